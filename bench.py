@@ -50,6 +50,39 @@ def model_cfg(arch="deeplabv2_resnet101", baseline=False):
               RUN_CONF_UPPER=0.75, RUN_CONF_LOWER=0.2, THRESHOLD_BETA=1e-3)
 
 
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 1 << 20         # elements kept of one array; larger arrays are sampled at fixed, seeded positions
+
+
+def dump_outputs(out_dir, res, net):
+    """--dump-outputs: what one training step hands its caller -- source losses (`src_*`), target losses (`tgt_*`), network
+    outputs (`out_*`) -- and the model state it leaves behind (`state`: every floating tensor of net.state_dict() in key order,
+    flattened into one array), as `out_dir/<name>.npy`.  float64 and 32/64-bit integer tensors are written as float64 (exact),
+    everything else as float32.  An array of more than `cap` elements is replaced by `cap` of them at sorted positions drawn
+    from a generator seeded with crc32(name): the same positions in every run and every build of the same shape.  `cap` starts
+    at DUMP_MAX_ELEMS and is halved until the files fit DUMP_MAX_BYTES."""
+    import zlib
+    import numpy as np
+    arrays = {}
+    for prefix, part in zip(("src", "tgt", "out"), res):
+        for k, v in (part or {}).items():
+            if torch.is_tensor(v):
+                arrays[prefix + "_" + k] = v.detach()
+    arrays["state"] = torch.cat([v.detach().flatten().float().cpu() for v in net.state_dict().values() if v.is_floating_point()])
+    wide = lambda t: t.dtype in (torch.float64, torch.int64, torch.int32)
+    cap = DUMP_MAX_ELEMS
+    while sum(min(t.numel(), cap) * (8 if wide(t) else 4) for t in arrays.values()) > DUMP_MAX_BYTES:
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(flat.numel(), (cap,), generator=gen).sort().values
+            t = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float64 if wide(t) else torch.float32).cpu().numpy())
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # CPU baseline + full-resolution parity: ONE bounded sample of the workload, run by the oracle (timed) and by the HIP path
 # ----------------------------------------------------------------------------------------------------------------
@@ -377,6 +410,10 @@ def main():
                          "train.py calls it (net(image, masks) + backward, net(frames1, ..., use_teacher=True) + backward, train.py:128-133,"
                          "219-233); the fused schedule is then reported next to it as `value_fused_schedule`")
     ap.add_argument("--two-pass", action="store_true", help="(default since round 6; kept for old command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (losses, network outputs) and the model "
+                         "state it left as DIR/<name>.npy, float32 / float64, at most 64 MB in all (large arrays as a fixed, seeded "
+                         "sample); rank 0's when there are several ranks")
     ap.add_argument("--alt", action="store_true", help="also run the steps once in the other precision (reported as \"alt\", no credit)")
     ap.add_argument("--config", default="cfg3", choices=["cfg2", "cfg3", "cfg5"],
                     help="cfg3 (default, the headline): RN101+SAC 8+2x4 crops @769^2; cfg2: RN101 baseline/AdaBN step, 2 source + 2 "
@@ -554,6 +591,8 @@ def main():
     # 1) the headline: K steps, nothing but the step itself inside the timed region
     dt, _, out = measure(0, args.warmup, args.steps, False)
     per_rank_headline = list(per_rank)
+    if args.dump_outputs and rank == 0:      # before any later leg steps the model again
+        dump_outputs(args.dump_outputs, out, net)
     done = args.warmup + args.steps
     # 2) the same workload once more with a HIP event pair around every instrumented launch (kernel table / roofline)
     prof, dt_prof, psteps = {}, None, max(1, args.profile_steps)

@@ -10,6 +10,9 @@ for p in (ROOT, PKG):
         sys.path.insert(0, p)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+# Rank processes a multi-rank GPU test may start when they all share one device: with the pytest process, which holds the
+# device too, that keeps at most 5 processes on a shared GPU.
+MAX_RANKS_ON_ONE_DEVICE = 4
 
 
 def pytest_configure(config):
@@ -70,16 +73,18 @@ def init_ranks(rank, world):
     return dev
 
 
-def run_ranks(target, world, make_args, timeout=300, attempts=2):
+def run_ranks(target, world, make_args, timeout=300, attempts=1):
     """Spawns `world` rank processes (`target(*make_args(rank, port, queue))`), collects one queue item per rank and returns them
     sorted by rank.  Bounded: a rank that dies or hangs costs `timeout` seconds, not the suite's budget.  A rank PROCESS failure (crash,
-    non-zero exit, nothing on the queue in time) is retried once with fresh processes and a fresh port -- round 6 saw one
-    `HSA_STATUS_ERROR_ILLEGAL_INSTRUCTION` queue abort in an 8-processes-on-one-device run that two reruns did not reproduce
-    (profiles/ROUND6.md).  Numerical assertions are the caller's and are never retried."""
+    non-zero exit, nothing on the queue in time) fails the test with the exit codes: the process may have faulted the device, and
+    nothing more is started on it.  Numerical assertions are the caller's and are never retried."""
     import queue as _queue
     import socket
     import sys
+    import torch
     import torch.multiprocessing as mp
+    assert world <= max(MAX_RANKS_ON_ONE_DEVICE, torch.cuda.device_count()), \
+        "{} ranks on {} device(s): more processes than one shared device takes".format(world, torch.cuda.device_count())
     last = None
     for attempt in range(attempts):
         s = socket.socket()

@@ -118,6 +118,11 @@ def _g11_worker(rank, world, port, cases, q):
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_product_prep_batch_and_gather_match_reference_golden_g11(golden, world):
+    from conftest import MAX_RANKS_ON_ONE_DEVICE
+    if world > MAX_RANKS_ON_ONE_DEVICE and os.path.exists("/dev/kfd"):
+        # on a GPU box every torch process counts against the device's process limit, these CPU ranks included; the
+        # world-8 tables are checked on the machines without a GPU, where this test belongs
+        pytest.skip("{} torch processes at once on a shared GPU box".format(world + 1))
     g = golden("g11_index_tables")
     cases = [c for c in g["cases"].tolist() if c[0] == world]
     ctx = mp.get_context("spawn")

@@ -1,6 +1,6 @@
 """dasac_hip.parallel.OverlappedDataParallel: the gradient all-reduce issued bucket by bucket from INSIDE the engine's
 backward pass (DistributedDataParallel's overlap, /root/reference/train.py:104,133,232).  Checked against (1) the bare
-module -- the flat-buffer gradient sink must not change a bit -- and (2) 2, 4 and 8 ranks on the one GPU of the box (gloo
+module -- the flat-buffer gradient sink must not change a bit -- and (2) 2, 3 and 4 ranks on the one GPU of the box (gloo
 transport; RCCL with a GPU per rank where the box has them) against a one-process emulation that averages the per-rank
 gradients by hand."""
 import os
@@ -108,7 +108,7 @@ def test_wrapper_refuses_trainable_parameters_it_would_never_reduce():
         wrapped(*src)
 
 
-# per-rank target batch of the multi-rank cases: (groups, views).  world 2 keeps the small historical case; worlds 4 and 8 run
+# per-rank target batch of the multi-rank cases: (groups, views).  world 2 keeps the small historical case; worlds 3 and 4 run
 # cfg-4's shape -- WHOLE groups per rank (N*L/world >= L: no SAC-specific collective, train.py:186-187), 2 groups x 4 views
 def _tgt_shape(world):
     return (1, 2) if world == 2 else (2, 4)
@@ -157,10 +157,11 @@ def _spawn(use_torch_ddp, world=2):
     return run_ranks(_rank_main, world, lambda r, port, q: (r, world, port, q, use_torch_ddp), timeout=240)
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 3, 4])
 def test_overlapped_reduction_equals_the_manual_mean_and_stock_ddp(world):
-    """world 4 / 8: cfg-4's per-rank shape with all ranks on the box's one device (gloo) -- bucket
-    bookkeeping, 1/world scaling and the construction-time broadcast run with rank >= 2 before any 8-GPU box sees them."""
+    """world 3 / 4: cfg-4's per-rank shape with all ranks on the box's one device (gloo) -- bucket
+    bookkeeping, 1/world scaling (inexact in binary at world 3) and the construction-time broadcast run with rank >= 2 before any
+    multi-GPU box sees them.  Worlds stay at 4 or less: the ranks share the device with the pytest process."""
     import driver
     got = _spawn(False, world)
     # construction synchronised every rank to rank 0 (parameters, synced and exempt buffers); all ranks end up identical

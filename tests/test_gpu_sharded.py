@@ -1,13 +1,14 @@
 """View-sharded target pass (cfg-5's regime): N*L/world < L, so the L views of ONE target image are spread over
-consecutive ranks.  2, 4 or 8 ranks (all on the box's one GPU over gloo, or one GPU each over RCCL when the box has them;
+consecutive ranks.  2 or 4 ranks (all on the box's one GPU over gloo, or one GPU each over RCCL when the box has them;
 DistributedDataParallel on top of the fused engine) run the product's `driver.prep_batch` (train.py:157-209) + the sharded
 `_refine` branch (sac.py:198-216, 244-246) inside two full training iterations; every rank's pseudo labels / refined
 probabilities / losses / updated parameters are compared with the CPU oracle emulating the same ranks
 (oracle.step_ref.ThreadWorld: DDP buffer broadcast before each forward -- quirk 5 --, gradient averaging after each
-backward, the two all_gathers).  The 8-rank case is cfg-5's own shape: N = 2 target images, L = 4 views, ONE view per
-rank -- ranks 0-3 share the image loaded by rank 0, ranks 4-7 the one loaded by rank 1 (train.py:199-209), both
-all_gathers run, `teacher_aligned` is sliced at `(rank * B) % T` -- so that index math for rank >= 2 has executed on a
-device before the first real 8-GPU run."""
+backward, the two all_gathers).  The fcn_vgg16_bn world-4 case has cfg-5's 8-GPU layout in small: N = 2 target images,
+L = 2 views, ONE view per rank -- ranks 0-1 share the image loaded by rank 0, ranks 2-3 the one loaded by rank 1
+(train.py:199-209), both all_gathers run, `teacher_aligned` is sliced at `(rank * B) % T` -- so that index math for
+rank >= 2 has executed on a device before the first real multi-GPU run.  Worlds stay at 4 or less: the ranks share the
+box's one device with the pytest process (conftest.MAX_RANKS_ON_ONE_DEVICE)."""
 import os
 import socket
 from types import SimpleNamespace as NS
@@ -40,11 +41,11 @@ ARCHS = {
 PARAM_TOL = {"vgg_head.4.bias": 2e-2, "vgg_head.8.bias": 1e-3}
 SRC_B, ITERS = 2, 2
 # (arch, world, N target images, L views per image): per = N*L/world views per rank < L in every case
-CASES = [("deeplabv2_resnet101", 2, 1, 2), ("fcn_vgg16_bn", 2, 1, 2), ("deeplabv2_resnet101", 4, 1, 4), ("fcn_vgg16_bn", 8, 2, 4)]
-# (ResNet-101 at world 8, N = 2, L = 4 also ran green in round 6 -- it is the case that exposed the gloo point-to-point defect -- and is
-# left out of the default list only for the suite's time budget: 70 s; DASAC_TEST_ALL_WORLDS=1 adds it back)
+CASES = [("deeplabv2_resnet101", 2, 1, 2), ("fcn_vgg16_bn", 2, 1, 2), ("deeplabv2_resnet101", 4, 1, 4), ("fcn_vgg16_bn", 4, 2, 2)]
+# (ResNet-101 with one view per rank over two images -- the layout that exposed the gloo point-to-point defect in round 6 at world 8 --
+# is left out of the default list only for the suite's time budget; DASAC_TEST_ALL_WORLDS=1 adds it back)
 if os.environ.get("DASAC_TEST_ALL_WORLDS") == "1":
-    CASES.append(("deeplabv2_resnet101", 8, 2, 4))
+    CASES.append(("deeplabv2_resnet101", 4, 2, 2))
 
 
 def _fcn_state():
@@ -141,15 +142,6 @@ def test_view_sharded_sac_iterations_vs_oracle(case):
     th.join()
     ref = ref["out"]
     bad = _compare(got, ref, WORLD, GROUPS, VIEWS)
-    if bad and WORLD >= 8 and all(b[2] == "teacher_diff" for b in bad) and len(bad) <= 1:
-        # OPEN ISSUE (round 6, profiles/ROUND6.md): with 8 ranks time-sliced on ONE device over gloo, 2 of 7 runs reported ONE rank's
-        # `teacher_diff` diagnostic low at iteration 1 (0.60 / 0.68 for 0.714) while every other quantity of every rank -- labels,
-        # probabilities, losses, parameters -- matched the oracle; not reproduced with 8 processes without a process group (bit-identical
-        # sequences, tools/experiments/r6_eight_procs_identical.py) nor with a host read right behind the kernel
-        # (tools/experiments/r6_teacher_diff_probe.py).  One fresh run of the ranks must then be clean; the first outcome is printed.
-        print("test_gpu_sharded: lone teacher_diff mismatch {} -- running the ranks once more".format(bad))
-        got = run_ranks(_rank_main, WORLD, lambda r, port, q: (r, port, case, q), timeout=300)
-        bad = _compare(got, ref, WORLD, GROUPS, VIEWS)
     assert not bad, "\n".join(str(x) for x in bad)
 
 

@@ -10,6 +10,17 @@ from conftest import rel_err
 T = torch.from_numpy
 
 
+@pytest.fixture(autouse=True)
+def _golden_thread_count():
+    """ATen's CPU convolution / batch-norm backward split their reductions by thread count: with 2 to 16 threads the stored
+    gradients are met to 1e-3 of the bound, from 32 threads on bn1's gradient misses it by 1.5x.  Pinned to 8 so that the
+    comparison does not depend on the host's core count."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(prev)
+
+
 def sampled(t, n=64):
     flat = t.detach().reshape(-1)
     m = min(n, flat.numel())
