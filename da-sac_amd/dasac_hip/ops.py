@@ -801,8 +801,9 @@ def bn_train_forward(z, bn, res=None, relu=False, update_running=True, tile_stat
     N, Cn = z.shape[0], z.shape[1]
     HW = z[0, 0].numel()
     scale, shift, mean, invstd = (_f32((Cn,), z) for _ in range(4))
-    mom = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
     upd = update_running and bn.track_running_stats
+    # momentum None: cumulative average over num_batches_tracked (absent when track_running_stats=False; nothing moves then)
+    mom = 0.0 if not upd else bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
     tail = (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr() if upd else None, bn.running_var.data_ptr() if upd else None,
             bn.num_batches_tracked.data_ptr() if upd else None, float(mom), float(bn.eps), Cn, scale.data_ptr(), shift.data_ptr(),
             mean.data_ptr(), invstd.data_ptr(), L.stream_ptr())

@@ -34,6 +34,8 @@ CASES = [
     ("3x3_qtap_splits", 256, 256, [(3, 3, 2, 2)], 1, (2, 40, 37)),
     ("3x3_d1_c19", 48, 19, [(3, 3, 1, 1)], 1, (3, 9, 13)),
     ("7x7_s2_stem", 3, 64, [(7, 7, 1, 3)], 2, (2, 65, 49)),
+    # the generic multi-branch conv_gemm at the ASPP geometry; the network runs ASPP classifiers through ops.ExpandedConv instead
+    # (test_gpu_expanded_conv.py)
     ("aspp4", 96, 19, [(3, 3, 6, 6), (3, 3, 12, 12), (3, 3, 18, 18), (3, 3, 24, 24)], 1, (2, 17, 21)),
     ("7x7_fcn_head", 16, 160, [(7, 7, 1, 3)], 1, (1, 8, 12)),
     ("7x7_fcn_head_cfg5", 512, 4096, [(7, 7, 1, 3)], 1, (1, 16, 32)),     # fcn.py:49 at its cfg-5 size (512x1024 crop / 32)
