@@ -352,15 +352,18 @@ class SourceCrops:
 
 class TargetCrops:
     """DataTarget's front half on the device, feeding an owned views.TargetViews with no host round trip.  Draws come from
-    the TargetViews' `rng` / `torch_gen`, so one seed reproduces DataTarget.__getitem__ after the image selection.
+    the TargetViews' `rng` / `torch_gen`, so one seed reproduces DataTarget.__getitem__ after the image selection -- and
+    from its first line when `sampler` (a sampling.TargetSampler) is given and `select(index)` opens every sample:
+    select -> front -> views consumes the python-`random` draws in DataTarget.__getitem__'s order.
     `make(image, label)` -> (frames1, gt, frames2, affine, affine_inv) as views.TargetViews.make; in eval mode
     (frames f32 [3,Hc,Wc], labels i64 [Hc,Wc]) with -1 under the padding mask."""
 
     IGNORE_LABEL = 255                  # dataloader_target.py:275-276: a missing label file is an all-255 label
 
     def __init__(self, crop_hw, group_size=4, train=True, target_scale=(1.0, 1.1), hflip=True, val_crop=False, seed=None,
-                 mean=MEAN, std=STD, **view_kw):
+                 mean=MEAN, std=STD, sampler=None, **view_kw):
         self.crop = (int(crop_hw[0]), int(crop_hw[1]))
+        self.sampler = sampler
         self.train, self.target_scale, self.hflip, self.val_crop = bool(train), tuple(target_scale), bool(hflip), bool(val_crop)
         self.views = views.TargetViews(self.crop, group_size, seed=seed, mean=mean, std=std, **view_kw)
         self.mean, self.std = tuple(mean), tuple(std)
@@ -383,6 +386,13 @@ class TargetCrops:
     @property
     def torch_gen(self):
         return self.views.torch_gen
+
+    def select(self, index):
+        """The image DataTarget.__getitem__(index) opens (dataloader_target.py:264-273): one `uniform` draw from this
+        object's own `rng`, before anything else of the sample."""
+        if self.sampler is None:
+            raise ValueError("TargetCrops.select needs a sampler (sampling.TargetSampler)")
+        return self.sampler.select(index, self.rng)
 
     def sample(self):
         return sample_target_front(self.rng, self.torch_gen, self.crop, self.target_scale, self.hflip)

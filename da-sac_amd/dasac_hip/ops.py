@@ -957,3 +957,23 @@ def iou_counts(logits_up, gt, counts=None, ignore_index=255):
     L.check(lib.dasac_iou_counts(logits_up.data_ptr(), gt.data_ptr(), B, Cn, H * W, int(ignore_index), counts.data_ptr(),
                                  L.stream_ptr()), "dasac_iou_counts")
     return counts
+
+
+def label_hist(labels_u8, counts=None):
+    """Per-image histogram of uint8 label maps ([B,H,W] or [H,W], contiguous, any alignment): accumulates the number of
+    pixels of every value 0..255 of image b into `counts[b]` (int64 [B,256]; allocated zeroed when None).  Value 255 is
+    counted like any other; sampling.weights_from_counts drops it."""
+    lib = L.load()
+    L.require_gpu(labels_u8, counts)
+    if labels_u8.dtype != torch.uint8 or labels_u8.dim() not in (2, 3) or not labels_u8.is_contiguous():
+        raise L.DasacError("label_hist takes a contiguous uint8 [B,H,W] or [H,W] tensor (got {} {}, contiguous: {})".format(
+            labels_u8.dtype, tuple(labels_u8.shape), labels_u8.is_contiguous()))
+    B = labels_u8.shape[0] if labels_u8.dim() == 3 else 1
+    HW = labels_u8.shape[-2] * labels_u8.shape[-1]
+    if counts is None:
+        counts = torch.zeros((B, 256), dtype=torch.int64, device=labels_u8.device)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (B, 256) or not counts.is_contiguous():
+        raise L.DasacError("label_hist accumulates into a contiguous int64 [{},256] tensor (got {} {})".format(
+            B, counts.dtype, tuple(counts.shape)))
+    L.check(lib.dasac_label_hist(labels_u8.data_ptr(), B, HW, counts.data_ptr(), L.stream_ptr()), "dasac_label_hist")
+    return counts

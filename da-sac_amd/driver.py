@@ -389,3 +389,38 @@ def summarise_iou(counts):
     tp, fp, fn = (counts[i].to(torch.float32).cpu() for i in range(3))
     floor = torch.tensor(1e-3)
     return tp / torch.maximum(floor, fn + fp + tp), tp / torch.maximum(floor, tp + fp), tp / torch.maximum(floor, tp + fn)
+
+
+def compute_sample_weights(net, batches, num_images, lut=None, teacher=False):
+    """Stage 2 of the reference's schedule (tools/compute_IS_weights.py on the masks infer_val.py wrote) without leaving the
+    device: per-image class pixel counts of the network's label maps, int64 [num_images,256] on the host -- the input of
+    sampling.weights_from_counts.  `batches` yields (image [B,3,H,W] on the device, global image indices [B] as a HOST
+    sequence / tensor); each batch is infer_label_maps -> ops.label_hist into the rows of one device table, one launch per
+    run of consecutive indices, with no host synchronisation inside the loop and one D2H copy at the end.  The network runs
+    in eval mode.  With a process group of world > 1 each rank passes its own slice of the images and the tables are summed
+    over ranks; a row no rank touched stays zero.  `lut` as infer_label_maps (e.g. CITYSCAPES_TRAIN_TO_ID: the counts land
+    in the Cityscapes-id bins)."""
+    import torch.distributed as dist
+    from dasac_hip import ops
+    core = net.module if hasattr(net, "module") else net
+    was = core.training
+    core.eval()
+    table = torch.zeros((num_images, 256), dtype=torch.int64, device=next(core.parameters()).device)
+    for image, index in batches:
+        index = [int(i) for i in (index.tolist() if torch.is_tensor(index) else index)]
+        assert len(index) == image.shape[0] and all(0 <= i < num_images for i in index), (index, num_images)
+        maps, _ = infer_label_maps(net, image, lut, teacher)
+        lo = 0
+        for hi in range(1, len(index) + 1):
+            if hi == len(index) or index[hi] != index[hi - 1] + 1:
+                ops.label_hist(maps[lo:hi], table[index[lo]:index[lo] + hi - lo])
+                lo = hi
+    core.train(was)
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return table.cpu()
+    # gloo moves device tensors with no ordering against the stream that fills them (see prep_batch): with it the HOST
+    # tables are summed; RCCL sums on the device, stream-ordered, before the one D2H copy.
+    if dist.get_backend() == "gloo":
+        table = table.cpu()
+    dist.all_reduce(table)
+    return table.cpu()

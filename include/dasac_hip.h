@@ -391,6 +391,13 @@ int dasac_dropout_planes(uint64_t seed, uint64_t offset, float p, int64_t planes
 int dasac_iou_counts(const float* logits, const int64_t* gt, int B, int C, int64_t HW, int ignore_index,
                      int64_t* counts, dasac_stream_t stream);
 
+/* Per-image class statistics for importance-sampled target selection (tools/compute_IS_weights.py:58-83, on the device):
+ * counts[b][v] += number of pixels of image b with value v, v in 0..255 (value 255 is counted too; callers drop it).
+ * labels: [B][HW] uint8, any alignment (an unaligned head and a tail of any length per image are read byte by byte, the
+ * rest 16 bytes per lane; no load leaves [labels, labels + B*HW)).  counts: [B][256] int64, accumulated into (the caller
+ * zeroes it).  Integer adds only: exact, and bit-identical from run to run.  No workspace. */
+int dasac_label_hist(const uint8_t* labels, int B, int64_t HW, int64_t* counts, dasac_stream_t stream);
+
 /* K augmented views of one target crop: the pixel work of DataTarget.__getitem__'s tail
  * (datasets/dataloader_target.py:281-306) -- GuidedRandHFlip (datasets/tf_target.py:141-157), MaskRandScaleCrop
  * (:159-239; Pillow resize BILINEAR for the image, NEAREST for label / padding mask) and ToTensorMask / Normalize /
