@@ -41,14 +41,21 @@ class ConvOp:
         # few output channels x many taps (ASPP): evaluate as dense 1x1 GEMMs over taps*Cp channels
         self.expanded = ops.ExpandedConv(self.spec) if (len(convs) > 1 and c0.out_channels <= 32 and c0.stride[0] == 1) else None
 
+    def owner_groups(self):
+        """(module, attribute) of every parameter in three groups: weights, biases, BN affine (gamma, beta)."""
+        return ([(c, "weight") for c in self.convs],
+                [(c, "bias") for c in self.convs] if self.has_bias else [],
+                [(self.bn, "weight"), (self.bn, "bias")] if self.bn is not None else [])
+
     def owners(self):
         """(module, attribute) of every parameter, in the order of params()."""
-        out = [(c, "weight") for c in self.convs]
-        if self.has_bias:
-            out += [(c, "bias") for c in self.convs]
-        if self.bn is not None:
-            out += [(self.bn, "weight"), (self.bn, "bias")]
-        return out
+        w, b, bn = self.owner_groups()
+        return w + b + bn
+
+    def name_index_groups(self):
+        """Names the three groups of `pidx` (the engine's index of every parameter, in the order of owners())."""
+        it = iter(self.pidx)
+        self.w_idx, self.b_idx, self.bn_idx = ([next(it) for _ in group] for group in self.owner_groups())
 
     def params(self):
         return [getattr(m, a) for m, a in self.owners()]
@@ -56,9 +63,138 @@ class ConvOp:
     def geometry(self):
         return tuple((c.kernel_size, c.dilation, c.padding, c.stride, c.bias is not None) for c in self.convs)
 
+    @property
+    def frozen_bn(self):
+        return self.bn is not None and not self.bn.training
+
+    @property
+    def refreshable(self):
+        """Single-branch, non-expanded: the whole-network refresh (Engine.refresh) rebuilds its fold and its packs."""
+        return self.expanded is None and len(self.convs) == 1
+
+    def inputs(self):
+        return [self.src] + ([self.res] if self.res is not None else [])
+
+    def tensors(self, c, h, w):
+        """(channels, height, width) of every tensor a forward over a [c, h, w] input creates; the output last."""
+        oh, ow = self.spec.out_hw(h, w)
+        return ([(self.expanded.E, oh, ow)] if self.expanded is not None else []) + [(self.spec.cout, oh, ow)]
+
+    def forward(self, eng, i, saved, keep):
+        acts, spec = saved["acts"], self.spec
+        xin = acts[self.src]
+        Nb, _, H, W = xin.shape
+        if self.expanded is not None:
+            _, bias_sum, _ = eng.fold(self)
+            return self.expanded.forward(xin, eng.packed(self, False), eng.table(self, H, W, False, xin.device), bias_sum)
+        OH, OW = spec.out_hw(H, W)
+        out = torch.empty((Nb, spec.cout, OH, OW), dtype=torch.float32, device=xin.device)
+        res = None if self.res is None else acts[self.res]
+        if self.bn is not None and self.bn.training:
+            # batch-statistics BN (baseline / AdaBN mode): raw conv, then stats -> normalise(+res)(+ReLU)
+            cb = self.convs[0].bias.detach() if self.has_bias else None
+            # the GEMM epilogue leaves the per-tile channel sums / sums of squares next to z: no statistics pass over z
+            ts = ops.tile_stats_buffer(Nb, spec.cout, OH, OW, xin.device) if ops.stats_ok(spec.cout, spec.cin) else None
+            z = ops.conv_gemm(xin, eng.packed(self, False, None), eng.table(self, H, W, False, xin.device), out, (OH, OW),
+                              spec.stride, spec.cout, spec.K, 1, cb, None, None, False, stats=ts)
+            out, stats = ops.bn_train_forward(z, self.bn, res, self.relu, tile_stats=ts)
+            if keep:
+                saved["aux"][i] = (z, stats)
+            return out
+        scale, shift, _ = eng.fold(self)
+        bits = None
+        if keep and self.relu and eng._bits_wanted[self.dst] and ops.bits_ok(spec.cout, spec.cin):
+            bits = ops.ReluBits(Nb, spec.cout, OH, OW, xin.device)
+            saved["bits"][self.dst] = bits
+        return ops.conv_gemm(xin, eng.packed(self, False, scale), eng.table(self, H, W, False, xin.device), out, (OH, OW),
+                             spec.stride, spec.cout, spec.K, 1, shift, res, None, self.relu, bits_out=bits)
+
+    def backward(self, eng, bp, i, dz):
+        """(a) parameter gradients, (b) data gradient into g[src], masked with the producer's ReLU pattern by the last consumer,
+        (c) residual hand-off and sink.done.  The expanded conv differs in the `ops` calls of (a) and (b) only."""
+        spec, ex = self.spec, self.expanded
+        xin = bp.acts[self.src]
+        H, W = xin.shape[2:]
+        dy_out = dz                       # gradient w.r.t. the op output (what a residual input receives)
+        if ex is not None:
+            d = ex.scatter(dz)
+            self._param_grads_expanded(eng, bp, d, dz, xin)
+        else:
+            dz, scale = self._param_grads(eng, bp, i, dz, xin)
+        if self.src != 0:
+            relu = bp.arrive(self.src)
+            if ex is not None:
+                mask = bp.relu_pattern(self.src, spec.cin, ex.E) if relu else None
+                bp.g[self.src] = ex.dgrad(d, eng.packed(self, True), eng.table(self, H, W, True, dz.device), (H, W),
+                                          res=bp.g.get(self.src), mask=mask)
+            else:
+                mask = (bp.relu_pattern(self.src, spec.cin, spec.cout) if spec.stride == 1 else bp.acts[self.src]) if relu else None
+                OH, OW = dz.shape[2:]
+                bp.g[self.src] = ops.conv_dgrad(spec, dz, None, (H, W), scale=scale, res=bp.g.get(self.src), mask=mask,
+                                                table=eng.table(self, OH, OW, True, dz.device),
+                                                packed=eng.packed(self, True, scale))
+        if self.res is not None:
+            bp.join(self.res, dy_out)
+        if bp.sink is not None:
+            bp.sink.done([j for j in self.pidx if bp.need[j]])
+
+    def _param_grads_expanded(self, eng, bp, d, dz, xin):
+        need = bp.need
+        if any(need[j] for j in self.w_idx):
+            bp.store(self.w_idx, self.expanded.wgrad(d, xin, [c.weight.detach() for c in self.convs],
+                                                     eng.table(self, xin.shape[2], xin.shape[3], False, xin.device),
+                                                     outs=[bp.dest(j) for j in self.w_idx]))
+        if any(need[j] for j in self.b_idx):
+            bp.fan_out(self.b_idx, ops.channel_sums(dz, out=bp.sums_dest(self.b_idx, True, self.spec.cout, dz.device)))
+
+    def _param_grads(self, eng, bp, i, dz, xin):
+        """Returns (gradient w.r.t. the conv output, the frozen BN's scale or None): what the data gradient starts from."""
+        spec, need, grads = self.spec, bp.need, bp.grads
+        w_idx, b_idx, bn_idx = self.w_idx, self.b_idx, self.bn_idx
+        train_bn = i in bp.aux
+        want_bias = any(need[j] for j in b_idx)
+        want_bn = any(need[j] for j in bn_idx)
+        if train_bn:
+            z, stats = bp.aux.pop(i)
+            dz, dg, db = ops.bn_train_backward(dz, z, stats, self.bn.weight.detach(), want_params=want_bn,
+                                               outs=(bp.dest(bn_idx[0]), bp.dest(bn_idx[1])) if want_bn else (None, None))
+            del z
+            if want_bn:
+                grads[bn_idx[0]], grads[bn_idx[1]] = dg, db
+            scale, invstd, want_bn = None, None, False        # what is left of BN below is the frozen one's
+        else:
+            scale, _, invstd = eng.fold(self)
+        bias_is_sums = train_bn or self.bn is None            # the bias gradient IS the channel sums of dz
+        sums, dot = None, None
+        if any(need[j] for j in w_idx) or want_bn:
+            if want_bn:
+                dot = bp.dot_slice(spec, dz.device)
+            if want_bn or want_bias:      # channel sums ride along with the wgrad kernel
+                sums = bp.sums_dest(b_idx, want_bias and bias_is_sums, spec.cout, dz.device)
+            bp.store(w_idx, ops.conv_wgrad(spec, dz, xin, [c.weight.detach() for c in self.convs], scale=scale, dot=dot,
+                                           table=eng.table(self, xin.shape[2], xin.shape[3], False, xin.device, wgrad=True),
+                                           sum_dz=sums, outs=[bp.dest(j) for j in w_idx]))
+        elif want_bias:
+            sums = ops.channel_sums(dz, out=bp.sums_dest(b_idx, bias_is_sums, spec.cout, dz.device))
+        if bias_is_sums:
+            if want_bias:
+                bp.fan_out(b_idx, sums)
+        elif want_bn or want_bias:
+            cb = self.convs[0].bias.detach() if self.has_bias else None
+            dg, db, dcb = ops.bn_param_grads(dot, sums, self.bn.running_mean, invstd, scale, cb,
+                                             want_gamma=want_bn, want_beta=want_bn, want_bias=want_bias,
+                                             outs=(bp.dest(bn_idx[0]) if want_bn else None, bp.dest(bn_idx[1]) if want_bn else None,
+                                                   bp.dest(b_idx[0]) if want_bias else None))
+            if want_bn:
+                grads[bn_idx[0]], grads[bn_idx[1]] = dg, db
+            if want_bias:
+                grads[b_idx[0]] = dcb
+        return dz, scale
+
 
 class PoolOp:
     kind = "pool"
+    relu = False
 
     def __init__(self, src, dst, k, s, p, ceil_mode):
         self.src, self.dst, self.k, self.s, self.p, self.ceil = src, dst, k, s, p, bool(ceil_mode)
@@ -66,9 +202,27 @@ class PoolOp:
     def params(self):
         return []
 
+    def inputs(self):
+        return [self.src]
+
+    def tensors(self, c, h, w):
+        return [(c, ops.pool_out(h, self.k, self.s, self.p, self.ceil), ops.pool_out(w, self.k, self.s, self.p, self.ceil))]
+
+    def forward(self, eng, i, saved, keep):
+        out, arg = ops.maxpool_fwd(saved["acts"][self.src], self.k, self.s, self.p, self.ceil)
+        if keep:
+            saved["aux"][i] = arg
+        return out
+
+    def backward(self, eng, bp, i, dz):
+        assert eng.consumers[self.src] == 1
+        bp.g[self.src] = ops.maxpool_bwd(dz, bp.acts[self.dst], bp.aux[i], bp.acts[self.src].shape[2:], self.k, self.s, self.p,
+                                         relu_mask=bp.arrive(self.src))
+
 
 class Up2AddOp:
     kind = "up2add"
+    relu = False
 
     def __init__(self, src, skip, dst):
         self.src, self.skip, self.dst = src, skip, dst
@@ -76,16 +230,56 @@ class Up2AddOp:
     def params(self):
         return []
 
+    def inputs(self):
+        return [self.src, self.skip]
+
+    def tensors(self, c, h, w):
+        return [(c, 2 * h, 2 * w)]
+
+    def forward(self, eng, i, saved, keep):
+        xin = saved["acts"][self.src]
+        up, _, _ = ops.upsample_softmax(xin, (2 * xin.shape[2], 2 * xin.shape[3]))
+        return ops.add(up, saved["acts"][self.skip], out=up)
+
+    def backward(self, eng, bp, i, dz):
+        bp.join(self.skip, dz)
+        bp.join(self.src, ops.upsample_bwd(dz, bp.acts[self.src].shape[2:]))
+
 
 class ScaleOp:
     """Dropout2d(p) in train mode: y = x * keep/(1-p) per (n, c) plane."""
     kind = "drop"
+    relu = False
 
     def __init__(self, src, dst, module):
         self.src, self.dst, self.module = src, dst, module
 
     def params(self):
         return []
+
+    def inputs(self):
+        return [self.src]
+
+    def tensors(self, c, h, w):
+        return [(c, h, w)]
+
+    def forward(self, eng, i, saved, keep):
+        xin, m = saved["acts"][self.src], self.module
+        if not (m.training and m.p > 0):
+            return xin
+        # ATen feature dropout (fcn.py:52,56): per (n, c) plane noise = bernoulli(1-p)/(1-p).  A test can pin
+        # the draw by setting `module.keep_mask` ([B,C], already divided by 1-p) -- parity needs equal masks.
+        keep_mask = getattr(m, "keep_mask", None)
+        if keep_mask is None:
+            keep_mask = ops.dropout_planes(xin.shape[0], xin.shape[1], m.p, xin.device)
+        assert tuple(keep_mask.shape) == tuple(xin.shape[:2]) and keep_mask.is_cuda
+        if keep:
+            saved["aux"][i] = keep_mask
+        return ops.scale_planes(xin, keep_mask)
+
+    def backward(self, eng, bp, i, dz):
+        m = bp.aux.get(i)
+        bp.join(self.src, dz if m is None else ops.scale_planes(dz, m))
 
 
 class Plan:
@@ -132,6 +326,19 @@ def _ver(t):
     return (t.data_ptr(), t._version)
 
 
+def _fold_key(op):
+    """What a cached fold of `op` was computed from: the frozen BN's vectors (and the conv bias), or the branch biases."""
+    if op.bn is None:
+        return tuple(_ver(c.bias) for c in op.convs)
+    bn, cb = op.bn, (op.convs[0].bias if op.has_bias else None)
+    return (_ver(bn.weight), _ver(bn.bias), _ver(bn.running_mean), _ver(bn.running_var), None if cb is None else _ver(cb))
+
+
+def _pack_key(op, scale):
+    """What a cached packed operand of `op` was computed from: the weights, the scale folded into them, the arithmetic."""
+    return tuple(_ver(c.weight) for c in op.convs) + ((_ver(scale),) if scale is not None else ()) + (ops.PRECISION,)
+
+
 def _copy_into(out, src):
     """A second parameter that receives the same gradient (the bias of every ASPP branch): its own tensor."""
     if out is None:
@@ -140,43 +347,107 @@ def _copy_into(out, src):
     return out
 
 
+class _BackwardPass:
+    """State of one Engine.backward, shared by the ops' backward methods: activation gradients `g` by slot, the consumers of
+    each slot still `pending`, the parameter gradients and where they are written."""
+
+    def __init__(self, eng, saved, grad_out, need, sink):
+        self.eng, self.need, self.sink = eng, need, sink
+        self.acts, self.aux, self.bits = saved["acts"], saved["aux"], saved.get("bits", {})
+        self.grads = [None] * len(eng.params)
+        self.g = {eng.plan.output: grad_out.contiguous()}
+        # the d-gamma dot terms of all frozen-BN convs are slices of ONE vector: [dot_rows, cout] partial rows per layer, every
+        # element written by the weight-gradient finish and added in a fixed order by bn_param_grads (no atomics, no fill)
+        self.dot_pool, self.dot_used = None, 0
+        self.dot_total = sum(ops.dot_rows(op.spec) * op.spec.cout for op in eng._convs if op.bn is not None and op.expanded is None)
+        self.pending = list(eng.consumers)
+        self.pending[eng.plan.output] = 0
+
+    def dest(self, j):
+        return self.sink.alloc(j) if (self.sink is not None and self.need[j]) else None
+
+    def store(self, idx, tensors):
+        for j, t in zip(idx, tensors):
+            if self.need[j]:
+                self.grads[j] = t
+
+    def sums_dest(self, b_idx, is_bias_grad, cout, device):
+        """Per-channel sums of dz: they ARE the bias gradient of a conv without (or with batch-statistics) BN -- then they
+        are written straight to that gradient's destination -- and an intermediate of bn_param_grads otherwise."""
+        wanted = [j for j in b_idx if self.need[j]]
+        out = self.dest(wanted[0]) if (is_bias_grad and wanted) else None
+        return torch.empty(cout, dtype=torch.float32, device=device) if out is None else out.view(cout)
+
+    def fan_out(self, b_idx, sums):
+        """Every branch bias sees the same gradient."""
+        wanted = [j for j in b_idx if self.need[j]]
+        for n_, j in enumerate(wanted):
+            self.grads[j] = sums if n_ == 0 else _copy_into(self.dest(j), sums)
+
+    def dot_slice(self, spec, device):
+        if self.dot_pool is None:
+            self.dot_pool = torch.empty(self.dot_total, dtype=torch.float32, device=device)
+        rows = ops.dot_rows(spec)
+        dot = self.dot_pool[self.dot_used:self.dot_used + rows * spec.cout].view(rows, spec.cout)
+        self.dot_used += rows * spec.cout
+        return dot
+
+    def relu_pattern(self, slot, M, Cx):
+        """What the data-gradient epilogue (output M channels, gathering Cx) masks with: the producer's bit mask when the
+        forward recorded one and this GEMM has the bit-mask variant, else the producer's fp32 output."""
+        b = self.bits.get(slot)
+        return b if (b is not None and ops.bits_ok(M, Cx)) else self.acts[slot]
+
+    def arrive(self, slot):
+        """One more consumer of `slot` delivers its gradient.  True when it is the last one and the slot's producer ends in
+        a ReLU: that consumer applies the pattern."""
+        self.pending[slot] -= 1
+        p = self.eng.producer[slot]
+        return self.pending[slot] == 0 and p is not None and p.relu
+
+    def join(self, slot, t):
+        """A pass-through consumer (residual / skip) hands its gradient to `slot`."""
+        relu = self.arrive(slot)
+        cur = self.g.get(slot)
+        t = t if cur is None else ops.add(cur, t)
+        self.g[slot] = ops.relu_mask(t, self.acts[slot]) if relu else t
+
+
 class Engine:
     """Executes a Plan.  Keeps per-layer caches of gather tables (by spatial size) and of packed
     weights / folded BN vectors (invalidated by the parameters' version counters)."""
 
     def __init__(self, plan):
         self.plan = plan
-        self.params, self._owners, self._geometry = [], [], []
+        self.params = []
         for op in plan.ops:
-            op.pidx = []
-            for p in op.params():
-                op.pidx.append(len(self.params))
-                self.params.append(p)
-            if op.kind == "conv":
-                self._owners += op.owners()
-                self._geometry.append((op, op.geometry()))
+            op.pidx = list(range(len(self.params), len(self.params) + len(op.params())))
+            self.params += op.params()
+        self._convs = [op for op in plan.ops if isinstance(op, ConvOp)]      # the ops that own parameters and caches
+        self._owners, self._geometry = [], []
+        for op in self._convs:
+            op.name_index_groups()
+            self._owners += op.owners()
+            self._geometry.append((op, op.geometry()))
         self.consumers = [0] * plan.n_slots
         self.producer = [None] * plan.n_slots
+        self.last_use = [0] * plan.n_slots
+        first_consumer = {}
         for i, op in enumerate(plan.ops):
             self.producer[op.dst] = op
-            for s in self._inputs(op):
+            for s in op.inputs():
                 self.consumers[s] += 1
-        self.last_use = [0] * plan.n_slots
-        for i, op in enumerate(plan.ops):
-            for s in self._inputs(op):
                 self.last_use[s] = i
+                first_consumer.setdefault(s, op)
         self.last_use[plan.output] = len(plan.ops)
         self._tables, self._packs, self._folds = {}, {}, {}
         self._refresh, self._fold_bufs = {}, {}
         # A ReLU conv's pattern is recorded as bits when the backward pass will apply it in a stride-1 data-gradient epilogue:
         # the mask is applied by the consumer that finishes LAST in backward order = the slot's FIRST consumer in plan order.
         self._bits_wanted = [False] * plan.n_slots
-        first_consumer = {}
-        for op in plan.ops:
-            for s_ in self._inputs(op):
-                first_consumer.setdefault(s_, (op, s_ == op.src))
-        for slot, (op, is_src) in first_consumer.items():
-            self._bits_wanted[slot] = bool(is_src and op.kind == "conv" and op.spec.stride == 1 and slot != 0)
+        for op in self._convs:
+            if first_consumer[op.src] is op and op.spec.stride == 1 and op.src != 0:
+                self._bits_wanted[op.src] = True
 
     def stale(self):
         """True when a module no longer holds the Parameter objects (or conv geometry) this engine captured:
@@ -185,80 +456,55 @@ class Engine:
         return any(getattr(m, a) is not p for (m, a), p in zip(self._owners, self.params)) or \
             any(op.geometry() != geo for op, geo in self._geometry)
 
-    @staticmethod
-    def _inputs(op):
-        if op.kind == "conv":
-            return [op.src] + ([op.res] if op.res is not None else [])
-        if op.kind == "up2add":
-            return [op.src, op.skip]
-        return [op.src]
-
     # ---------------------------------------------------------------- caches
     def table(self, op, h, w, transposed, device, wgrad=False):
-        """Gather table; the forward / data-gradient GEMMs may use the chunk-major K order, the weight
-        gradient always the tap-major one."""
-        order = 0 if wgrad else ops.gemm_order(op.spec, transposed)
+        """Gather table (of the 1x1 GEMM over the expanded channels for an expanded conv); the forward / data-gradient GEMMs
+        may use the chunk-major K order, the weight gradient always the tap-major one."""
+        spec = op.spec if op.expanded is None else op.expanded.spec1
+        order = 0 if wgrad else ops.gemm_order(spec, transposed)
         key = (id(op), h, w, transposed, device.index, order)
         t = self._tables.get(key)
         if t is None:
-            t = ops.conv_table(op.spec, h, w, transposed, device, order)
+            t = ops.conv_table(spec, h, w, transposed, device, order)
             self._tables[key] = t
         return t
+
+    @staticmethod
+    def _cached(store, slot, key, build, *args):
+        """store[slot] = (key, value, args): the value when its key still holds, else build(old value or None, *args) --
+        a rebuild writes into the old buffer.  `args` stay alive with the entry (a scale vector's address is part of its key)."""
+        ent = store.get(slot)
+        if ent is None or ent[0] != key:
+            ent = store[slot] = (key, build(None if ent is None else ent[1], *args), args)
+        return ent[1]
 
     def fold(self, op):
         """(scale, shift, invstd) of the frozen BN (plus conv bias), or (None, bias_sum, None)."""
+        if op.bn is None and (not op.has_bias or len(op.convs) == 1):
+            return None, (op.convs[0].bias.detach() if op.has_bias else None), None
+        return self._cached(self._folds, id(op), _fold_key(op), self._build_fold, op)
+
+    @staticmethod
+    def _build_fold(old, op):
         if op.bn is None:
-            if not op.has_bias:
-                return None, None, None
-            if len(op.convs) == 1:
-                return None, op.convs[0].bias.detach(), None
-            key = ("bsum", id(op)) + tuple(_ver(c.bias) for c in op.convs)
-            ent = self._folds.get(id(op))
-            if ent is None or ent[0] != key:
-                acc = op.convs[0].bias.detach()
-                for c in op.convs[1:]:
-                    acc = ops.add(acc, c.bias.detach())
-                ent = (key, (None, acc, None))
-                self._folds[id(op)] = ent
-            return ent[1]
-        bn, cb = op.bn, (op.convs[0].bias if op.has_bias else None)
-        key = (_ver(bn.weight), _ver(bn.bias), _ver(bn.running_mean), _ver(bn.running_var), None if cb is None else _ver(cb))
-        ent = self._folds.get(id(op))
-        if ent is None or ent[0] != key:
-            ent = (key, ops.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-                                    None if cb is None else cb.detach()))
-            self._folds[id(op)] = ent
-        return ent[1]
-
-    def table_e(self, op, h, w, transposed, device):
-        key = (id(op), "e", h, w, transposed, device.index)
-        t = self._tables.get(key)
-        if t is None:
-            t = ops.conv_table(op.expanded.spec1, h, w, transposed, device)
-            self._tables[key] = t
-        return t
-
-    def packed_e(self, op, transposed):
-        key = tuple(_ver(c.weight) for c in op.convs) + (ops.PRECISION,)
-        slot = (id(op), "e", transposed)
-        ent = self._packs.get(slot)
-        if ent is None or ent[0] != key:
-            buf = op.expanded.pack([c.weight.detach() for c in op.convs], transposed, out=None if ent is None else ent[1])
-            ent = (key, buf)
-            self._packs[slot] = ent
-        return ent[1]
+            acc = op.convs[0].bias.detach()
+            for c in op.convs[1:]:
+                acc = ops.add(acc, c.bias.detach())
+            return None, acc, None
+        bn = op.bn
+        return ops.bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
+                           op.convs[0].bias.detach() if op.has_bias else None)
 
     def packed(self, op, transposed, scale=None):
-        key = tuple(_ver(c.weight) for c in op.convs) + ((_ver(scale),) if scale is not None else ()) + (ops.PRECISION,)
-        slot = (id(op), transposed)
-        ent = self._packs.get(slot)
-        if ent is None or ent[0] != key:
-            buf = None if ent is None else ent[1]
-            buf = ops.conv_pack(op.spec, [c.weight.detach() for c in op.convs], transposed, scale, out=buf,
-                                order=ops.gemm_order(op.spec, transposed))
-            ent = (key, buf, scale)      # keep `scale` alive: its data_ptr is part of the key
-            self._packs[slot] = ent
-        return ent[1]
+        """Packed weight operand of the forward (transposed: the data-gradient) GEMM, `scale` folded in."""
+        return self._cached(self._packs, (id(op), transposed), _pack_key(op, scale), self._build_pack, op, transposed, scale)
+
+    @staticmethod
+    def _build_pack(old, op, transposed, scale):
+        weights = [c.weight.detach() for c in op.convs]
+        if op.expanded is not None:
+            return op.expanded.pack(weights, transposed, out=old)
+        return ops.conv_pack(op.spec, weights, transposed, scale, out=old, order=ops.gemm_order(op.spec, transposed))
 
     def largest_tensor_bytes(self, Nb, H, W):
         """Bytes of the largest activation (or expanded-conv intermediate) a pass over an [Nb, *, H, W] input creates.  The conv
@@ -267,20 +513,9 @@ class Engine:
         shapes = {0: (None, H, W)}
         biggest = 0
         for op in self.plan.ops:
-            _, h, w = shapes[op.src]
-            if op.kind == "conv":
-                oh, ow = op.spec.out_hw(h, w)
-                c = op.spec.cout
-                if op.expanded is not None:
-                    biggest = max(biggest, Nb * op.expanded.E * oh * ow * 4)
-            elif op.kind == "pool":
-                oh, ow, c = ops.pool_out(h, op.k, op.s, op.p, op.ceil), ops.pool_out(w, op.k, op.s, op.p, op.ceil), shapes[op.src][0]
-            elif op.kind == "up2add":
-                oh, ow, c = 2 * h, 2 * w, shapes[op.src][0]
-            else:
-                oh, ow, c = h, w, shapes[op.src][0]
-            shapes[op.dst] = (c, oh, ow)
-            biggest = max(biggest, Nb * (c or 1) * oh * ow * 4)
+            made = op.tensors(*shapes[op.src])
+            shapes[op.dst] = made[-1]
+            biggest = max([biggest] + [Nb * (c or 1) * h * w * 4 for c, h, w in made])
         return biggest
 
     # ---------------------------------------------------------------- whole-network refresh of folds / packs
@@ -288,18 +523,18 @@ class Engine:
         """Device job tables for `ops.refresh_network`: one fold job per frozen-BN conv, one pack job per (conv, layout) for
         every single-branch, non-expanded conv.  Output buffers are persistent (their pointers sit in the tables)."""
         # batch-statistics BN layers (baseline / AdaBN mode) fold nothing into the weights: their convs are packed un-scaled
-        bn_mode = tuple(bool(op.bn is not None and op.bn.training) for op in self.plan.ops if op.kind == "conv")
+        bn_mode = tuple(bool(op.bn is not None and op.bn.training) for op in self._convs)
         key = (device.index, bool(transposed), bn_mode)
         plan = self._refresh.get(key)
         if plan is not None and plan["ptrs"] == self._refresh_ptrs():
             return plan
         lib = L.load()
         fold_jobs, pack_jobs, fold_ops, pack_slots = [], [], [], []
-        for op in self.plan.ops:
-            if op.kind != "conv" or op.expanded is not None or len(op.convs) != 1:
+        for op in self._convs:
+            if not op.refreshable:
                 continue
             scale = None
-            if op.bn is not None and not op.bn.training:
+            if op.frozen_bn:
                 ent = self._fold_bufs.get(id(op))
                 if ent is None:
                     C = op.spec.cout
@@ -328,11 +563,10 @@ class Engine:
 
     def _refresh_ptrs(self):
         out = []
-        for op in self.plan.ops:
-            if op.kind == "conv":
-                out += [p.data_ptr() for p in op.params()]
-                if op.bn is not None:
-                    out += [op.bn.running_mean.data_ptr(), op.bn.running_var.data_ptr()]
+        for op in self._convs:
+            out += [p.data_ptr() for p in op.params()]
+            if op.bn is not None:
+                out += [op.bn.running_mean.data_ptr(), op.bn.running_var.data_ptr()]
         return tuple(out)
 
     def refresh(self, device, transposed):
@@ -344,22 +578,15 @@ class Engine:
         same launch; only frozen BNs have a fold job."""
         if ops.PRECISION != "fp32":
             return
-        convs = [op for op in self.plan.ops if op.kind == "conv" and op.expanded is None and len(op.convs) == 1]
+        convs = [op for op in self._convs if op.refreshable]
         if len(convs) < 8:
             return
-        frozen = lambda op: op.bn is not None and not op.bn.training
         # stale = the cached key no longer matches the parameters' version counters
-        def pack_key(op, scale):
-            return (_ver(op.convs[0].weight),) + ((_ver(scale),) if scale is not None else ()) + (ops.PRECISION,)
-
-        def fold_key(op):
-            bn, cb = op.bn, (op.convs[0].bias if op.has_bias else None)
-            return (_ver(bn.weight), _ver(bn.bias), _ver(bn.running_mean), _ver(bn.running_var), None if cb is None else _ver(cb))
         for op in convs:                                     # all-or-nothing: the first fresh layer ends the check
             ent = self._packs.get((id(op), False))
-            sc = self._folds.get(id(op)) if frozen(op) else None
-            fresh_fold = (not frozen(op)) or (sc is not None and sc[0] == fold_key(op))
-            if fresh_fold and ent is not None and ent[0] == pack_key(op, sc[1][0] if frozen(op) else None):
+            sc = self._folds.get(id(op)) if op.frozen_bn else None
+            fresh_fold = (not op.frozen_bn) or (sc is not None and sc[0] == _fold_key(op))
+            if fresh_fold and ent is not None and ent[0] == _pack_key(op, sc[1][0] if op.frozen_bn else None):
                 # (the forward layout may have been refreshed alone by a no-grad pass -- AdaBN's target forward right after the
                 # optimiser step: the data-gradient layout is then still stale, and one more launch beats 104 per-layer ones)
                 ent_t = self._packs.get((id(op), True)) if transposed else ent
@@ -370,9 +597,9 @@ class Engine:
         for op in plan["fold_ops"]:
             ent = self._fold_bufs[id(op)]
             ops.bump_versions([ent[0]])                      # the scale vector is part of the pack keys: it has new contents
-            self._folds[id(op)] = (fold_key(op), ent)
+            self._folds[id(op)] = (_fold_key(op), ent, None)
         for slot, op, buf, scale in plan["pack_slots"]:
-            self._packs[slot] = (pack_key(op, scale), buf, scale)
+            self._packs[slot] = (_pack_key(op, scale), buf, scale)
 
     # ---------------------------------------------------------------- forward
     def forward(self, x, keep):
@@ -382,65 +609,9 @@ class Engine:
         acts = {0: x}
         saved = {"acts": acts, "aux": {}, "bits": {}}
         for i, op in enumerate(self.plan.ops):
-            xin = acts[op.src]
-            if op.kind == "conv":
-                Nb, _, H, W = xin.shape
-                OH, OW = op.spec.out_hw(H, W)
-                if op.expanded is not None:
-                    _, bias_sum, _ = self.fold(op)
-                    acts[op.dst] = op.expanded.forward(xin, self.packed_e(op, False), self.table_e(op, H, W, False, xin.device), bias_sum)
-                    if not keep:
-                        for s_ in self._inputs(op):
-                            if self.last_use[s_] == i and s_ != 0:
-                                del acts[s_]
-                    continue
-                out = torch.empty((Nb, op.spec.cout, OH, OW), dtype=torch.float32, device=xin.device)
-                if op.bn is not None and op.bn.training:
-                    # batch-statistics BN (baseline / AdaBN mode): raw conv, then stats -> normalise(+res)(+ReLU)
-                    cb = op.convs[0].bias.detach() if op.has_bias else None
-                    # the GEMM epilogue leaves the per-tile channel sums / sums of squares next to z: no statistics pass over z
-                    ts = ops.tile_stats_buffer(Nb, op.spec.cout, OH, OW, xin.device) if ops.stats_ok(op.spec.cout, op.spec.cin) else None
-                    ops.conv_gemm(xin, self.packed(op, False, None), self.table(op, H, W, False, xin.device), out, (OH, OW),
-                                  op.spec.stride, op.spec.cout, op.spec.K, 1, cb, None, None, False, stats=ts)
-                    z = out
-                    out, stats = ops.bn_train_forward(z, op.bn, None if op.res is None else acts[op.res], op.relu, tile_stats=ts)
-                    if keep:
-                        saved["aux"][i] = (z, stats)
-                else:
-                    scale, shift, _ = self.fold(op)
-                    bits = None
-                    if keep and op.relu and self._bits_wanted[op.dst] and ops.bits_ok(op.spec.cout, op.spec.cin):
-                        bits = ops.ReluBits(Nb, op.spec.cout, OH, OW, xin.device)
-                        saved["bits"][op.dst] = bits
-                    ops.conv_gemm(xin, self.packed(op, False, scale), self.table(op, H, W, False, xin.device), out, (OH, OW),
-                                  op.spec.stride, op.spec.cout, op.spec.K, 1, shift,
-                                  None if op.res is None else acts[op.res], None, op.relu, bits_out=bits)
-            elif op.kind == "pool":
-                out, arg = ops.maxpool_fwd(xin, op.k, op.s, op.p, op.ceil)
-                if keep:
-                    saved["aux"][i] = arg
-            elif op.kind == "up2add":
-                up, _, _ = ops.upsample_softmax(xin, (2 * xin.shape[2], 2 * xin.shape[3]))
-                out = ops.add(up, acts[op.skip], out=up)
-            elif op.kind == "drop":
-                m = op.module
-                if m.training and m.p > 0:
-                    # ATen feature dropout (fcn.py:52,56): per (n, c) plane noise = bernoulli(1-p)/(1-p).  A test can pin
-                    # the draw by setting `module.keep_mask` ([B,C], already divided by 1-p) -- parity needs equal masks.
-                    keep_mask = getattr(m, "keep_mask", None)
-                    if keep_mask is None:
-                        keep_mask = ops.dropout_planes(xin.shape[0], xin.shape[1], m.p, xin.device)
-                    assert tuple(keep_mask.shape) == tuple(xin.shape[:2]) and keep_mask.is_cuda
-                    out = ops.scale_planes(xin, keep_mask)
-                    if keep:
-                        saved["aux"][i] = keep_mask
-                else:
-                    out = xin
-            else:
-                raise AssertionError(op.kind)
-            acts[op.dst] = out
+            acts[op.dst] = op.forward(self, i, saved, keep)
             if not keep:
-                for s in self._inputs(op):
+                for s in op.inputs():
                     if self.last_use[s] == i and s != 0:
                         del acts[s]
         return acts[self.plan.output], saved
@@ -455,168 +626,18 @@ class Engine:
         are complete -- `sink.alloc(j)` returns the destination of parameter j (a slice of one flat reduction buffer),
         `sink.done(indices)` is called after each op, in backward order, so that a bucket's all-reduce can start while
         the layers below it are still being differentiated (DistributedDataParallel's overlap, train.py:104,133,232)."""
-        acts, aux = saved["acts"], saved["aux"]
-        bits = saved.get("bits", {})
-        grads = [None] * len(self.params)
-
-        def relu_pattern(slot, M, Cx):
-            """What the data-gradient epilogue (output M channels, gathering Cx) masks with: the producer's bit mask when the
-            forward recorded one and this GEMM has the bit-mask variant, else the producer's fp32 output."""
-            b = bits.get(slot)
-            return b if (b is not None and ops.bits_ok(M, Cx)) else acts[slot]
-
-        def dest(j):
-            return sink.alloc(j) if (sink is not None and need[j]) else None
-
-        def sums_dest(b_idx, is_bias_grad, cout, device):
-            """Per-channel sums of dz: they ARE the bias gradient of a conv without (or with batch-statistics) BN -- then they
-            are written straight to that gradient's destination -- and an intermediate of bn_param_grads otherwise."""
-            wanted = [j for j in b_idx if need[j]]
-            out = dest(wanted[0]) if (is_bias_grad and wanted) else None
-            return torch.empty(cout, dtype=torch.float32, device=device) if out is None else out.view(cout)
-
-        g = {self.plan.output: grad_out.contiguous()}
-        # the d-gamma dot terms of all frozen-BN convs are slices of ONE vector: [dot_rows, cout] partial rows per layer, every
-        # element written by the weight-gradient finish and added in a fixed order by bn_param_grads (no atomics, no fill)
-        dot_pool, dot_used = None, 0
-        dot_total = sum(ops.dot_rows(op.spec) * op.spec.cout for op in self.plan.ops
-                        if op.kind == "conv" and op.bn is not None and op.expanded is None)
-        pending = list(self.consumers)
-        pending[self.plan.output] = 0
-
-        def relu_producer(slot):
-            p = self.producer[slot]
-            return p is not None and p.kind == "conv" and p.relu
-
-        def join_identity(slot, t):
-            """A pass-through consumer (residual / skip) hands its gradient to `slot`."""
-            pending[slot] -= 1
-            cur = g.get(slot)
-            t = t if cur is None else ops.add(cur, t)
-            if pending[slot] == 0 and relu_producer(slot):
-                t = ops.relu_mask(t, acts[slot])
-            g[slot] = t
-
+        bp = _BackwardPass(self, saved, grad_out, need, sink)
         for i in range(len(self.plan.ops) - 1, -1, -1):
             op = self.plan.ops[i]
-            dz = g.pop(op.dst, None)
+            dz = bp.g.pop(op.dst, None)
             if dz is None:
                 continue
-            assert pending[op.dst] == 0
+            assert bp.pending[op.dst] == 0
             if trace is not None:
                 trace[op.dst] = dz
-            xin = acts[op.src]
-            if op.kind == "conv":
-                spec = op.spec
-                Nb, _, H, W = xin.shape
-                if op.expanded is not None:
-                    ex, nw_ = op.expanded, len(op.convs)
-                    d = ex.scatter(dz)
-                    if any(need[j] for j in op.pidx[:nw_]):
-                        dws = ex.wgrad(d, xin, [c.weight.detach() for c in op.convs], self.table_e(op, H, W, False, xin.device),
-                                       outs=[dest(j) for j in op.pidx[:nw_]])
-                        for j, dw in zip(op.pidx[:nw_], dws):
-                            if need[j]:
-                                grads[j] = dw
-                    if op.has_bias and any(need[j] for j in op.pidx[nw_:]):
-                        wanted = [j for j in op.pidx[nw_:] if need[j]]
-                        sums = ops.channel_sums(dz, out=dest(wanted[0]))
-                        for n_, j in enumerate(wanted):              # every branch bias sees the same gradient
-                            grads[j] = sums if n_ == 0 else _copy_into(dest(j), sums)
-                    if op.src != 0:
-                        pending[op.src] -= 1
-                        last = pending[op.src] == 0
-                        mask = relu_pattern(op.src, spec.cin, ex.E) if (last and relu_producer(op.src)) else None
-                        g[op.src] = ex.dgrad(d, self.packed_e(op, True), self.table_e(op, H, W, True, dz.device), (H, W),
-                                             res=g.get(op.src), mask=mask)
-                    acts.pop(op.dst, None)
-                    if sink is not None:
-                        sink.done([j for j in op.pidx if need[j]])
-                    continue
-                dy_out = dz                       # gradient w.r.t. the op output (what a residual input receives)
-                train_bn = i in aux
-                nw = len(op.convs)
-                if train_bn:
-                    z, stats = aux.pop(i)
-                    bn_tail = op.pidx[nw + (nw if op.has_bias else 0):]
-                    bn_need = any(need[j] for j in bn_tail)
-                    dz, dg, db = ops.bn_train_backward(dz, z, stats, op.bn.weight.detach(), want_params=bn_need,
-                                                       outs=(dest(bn_tail[0]), dest(bn_tail[1])) if bn_need else (None, None))
-                    del z
-                    scale, shift, invstd = None, None, None
-                else:
-                    scale, shift, invstd = self.fold(op)
-                w_need = [need[j] for j in op.pidx[:nw]]
-                rest = op.pidx[nw:]
-                b_idx = rest[:nw] if op.has_bias else []
-                bn_idx = rest[len(b_idx):]
-                want_bn = (not train_bn) and op.bn is not None and any(need[j] for j in bn_idx)
-                want_bias = any(need[j] for j in b_idx)
-                if train_bn and bn_need:
-                    grads[bn_idx[0]], grads[bn_idx[1]] = dg, db
-                sums, dot = None, None
-                if any(w_need) or want_bn:
-                    if want_bn:
-                        if dot_pool is None:
-                            dot_pool = torch.empty(dot_total, dtype=torch.float32, device=dz.device)
-                        rows = ops.dot_rows(spec)
-                        dot = dot_pool[dot_used:dot_used + rows * spec.cout].view(rows, spec.cout)
-                        dot_used += rows * spec.cout
-                    if want_bn or want_bias:      # channel sums ride along with the wgrad kernel
-                        sums = sums_dest(b_idx, want_bias and (train_bn or op.bn is None), spec.cout, dz.device)
-                    dws = ops.conv_wgrad(spec, dz, xin, [c.weight.detach() for c in op.convs], scale=scale, dot=dot,
-                                         table=self.table(op, H, W, False, xin.device, wgrad=True), sum_dz=sums,
-                                         outs=[dest(j) for j in op.pidx[:nw]])
-                    for j, dw in zip(op.pidx[:nw], dws):
-                        if need[j]:
-                            grads[j] = dw
-                elif want_bias:
-                    sums = ops.channel_sums(dz, out=sums_dest(b_idx, train_bn or op.bn is None, spec.cout, dz.device))
-                if train_bn:
-                    if want_bias:
-                        grads[b_idx[0]] = sums
-                elif op.bn is not None:
-                    cb = op.convs[0].bias.detach() if op.has_bias else None
-                    dg, db, dcb = ops.bn_param_grads(dot, sums, op.bn.running_mean, invstd, scale, cb,
-                                                     want_gamma=want_bn, want_beta=want_bn, want_bias=want_bias,
-                                                     outs=(dest(bn_idx[0]) if want_bn else None, dest(bn_idx[1]) if want_bn else None,
-                                                           dest(b_idx[0]) if want_bias else None)) \
-                        if (want_bn or want_bias) else (None, None, None)
-                    if want_bn:
-                        grads[bn_idx[0]], grads[bn_idx[1]] = dg, db
-                    if want_bias:
-                        grads[b_idx[0]] = dcb
-                elif want_bias:
-                    wanted = [j for j in b_idx if need[j]]
-                    for n_, j in enumerate(wanted):       # every branch bias sees the same gradient
-                        grads[j] = sums if n_ == 0 else _copy_into(dest(j), sums)
-                if op.src != 0:
-                    pending[op.src] -= 1
-                    last = pending[op.src] == 0
-                    mask = (relu_pattern(op.src, spec.cin, spec.cout) if spec.stride == 1 else acts[op.src]) \
-                        if (last and relu_producer(op.src)) else None
-                    OH, OW = dz.shape[2:]
-                    g[op.src] = ops.conv_dgrad(spec, dz, None, (H, W), scale=scale, res=g.get(op.src), mask=mask,
-                                               table=self.table(op, OH, OW, True, dz.device),
-                                               packed=self.packed(op, True, scale))
-                if op.res is not None:
-                    join_identity(op.res, dy_out)
-                if sink is not None:
-                    sink.done([j for j in op.pidx if need[j]])
-            elif op.kind == "pool":
-                assert self.consumers[op.src] == 1
-                pending[op.src] -= 1
-                g[op.src] = ops.maxpool_bwd(dz, acts[op.dst], aux[i], xin.shape[2:], op.k, op.s, op.p,
-                                            relu_mask=relu_producer(op.src))
-            elif op.kind == "up2add":
-                join_identity(op.skip, dz)
-                join_identity(op.src, ops.upsample_bwd(dz, xin.shape[2:]))
-            elif op.kind == "drop":
-                m = aux.get(i)
-                join_identity(op.src, dz if m is None else ops.scale_planes(dz, m))
-            # the activation of this op's output is no longer needed
-            acts.pop(op.dst, None)
-        return grads
+            op.backward(self, bp, i, dz)
+            bp.acts.pop(op.dst, None)      # the activation of this op's output is no longer needed
+        return bp.grads
 
 
 class _PlanFunction(torch.autograd.Function):

@@ -136,7 +136,7 @@ def gemm_order(spec, transposed):
     """K order of the forward / data-gradient GEMM: chunk-major (1) for multi-tap convs whose gathered channel
     count is a multiple of 16, tap-major (0) otherwise.  The weight gradient always uses tap-major tables."""
     C = spec.cout if transposed else spec.cin
-    return 1 if (spec.taps > 1 and C % 16 == 0 and os.environ.get("DASAC_KORDER", "1") != "0") else 0
+    return 1 if (spec.taps > 1 and C % 16 == 0) else 0
 
 
 def conv_table(spec, plane_h, plane_w, transposed, device, order=0):
@@ -152,6 +152,14 @@ def conv_table(spec, plane_h, plane_w, transposed, device, order=0):
     return table
 
 
+def _branch_taps(spec):
+    """(taps, first tap on the concatenated K axis) of every branch."""
+    tap0 = 0
+    for kh, kw, _, _ in spec.branches:
+        yield kh * kw, tap0
+        tap0 += kh * kw
+
+
 def conv_pack(spec, weights, transposed, scale=None, out=None, order=0):
     """Packs the branch weight tensors [Cout,Cin,kh,kw] into the [Kpad][Mpad] GEMM operand."""
     lib = L.load()
@@ -161,20 +169,16 @@ def conv_pack(spec, weights, transposed, scale=None, out=None, order=0):
     shape = (lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M))
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=weights[0].device)
-    tap0 = 0
-    for w, (kh, kw, _, _) in zip(weights, spec.branches):
-        L.check(lib.dasac_conv_pack(_c(w).data_ptr(), L.ptr(scale), spec.cout, spec.cin, kh * kw, tap0, spec.taps,
+    for w, (taps, tap0) in zip(weights, _branch_taps(spec)):
+        L.check(lib.dasac_conv_pack(_c(w).data_ptr(), L.ptr(scale), spec.cout, spec.cin, taps, tap0, spec.taps,
                                     int(transposed), int(order), out.data_ptr(), L.stream_ptr()), "dasac_conv_pack")
-        tap0 += kh * kw
     return _finish_pack(out, M, K)
 
 
-RELU_BITS = os.environ.get("DASAC_RELU_BITS", "1") != "0"      # ReLU patterns as bit masks (1/32 of the bytes) between fwd and dgrad
-
-
 def bits_ok(M, Cx):
-    """True when the fp32 conv GEMM for an output of M channels over Cx gathered channels has a bit-mask variant."""
-    return RELU_BITS and PRECISION == "fp32" and bool(L.load().dasac_conv_gemm_bits_ok(int(M), int(Cx)))
+    """True when the fp32 conv GEMM for an output of M channels over Cx gathered channels has a bit-mask variant
+    (ReLU patterns as bit masks: 1/32 of the bytes between forward and data gradient)."""
+    return PRECISION == "fp32" and bool(L.load().dasac_conv_gemm_bits_ok(int(M), int(Cx)))
 
 
 class ReluBits:
@@ -187,7 +191,7 @@ class ReluBits:
 
 def stats_ok(M, Cx):
     """True when the conv GEMM for M output channels over Cx gathered channels can leave per-tile channel statistics."""
-    return PRECISION == "fp32" and os.environ.get("DASAC_GEMM_STATS", "1") != "0" and bool(L.load().dasac_conv_gemm_stats_ok(int(M), int(Cx)))
+    return PRECISION == "fp32" and bool(L.load().dasac_conv_gemm_stats_ok(int(M), int(Cx)))
 
 
 def tile_stats_buffer(Nb, M, OH, OW, device):
@@ -221,36 +225,35 @@ def conv_gemm(x, packed, table, out, grid_hw, stride, M, K, ostride=1, shift=Non
     fn = lib.dasac_conv_gemm_x3 if getattr(packed, "dasac_x3", False) else lib.dasac_conv_gemm
     tag = (M, K, Nb * OH * OW, stride, ostride, res is not None, mask is not None or mask_bits is not None)
 
-    def launch(span, pix_begin, pix_count, schedule):
-        n = pix_count if pix_count else Nb * OH * OW - pix_begin
-        frac = n / float(Nb * OH * OW)
-        nbytes = 4.0 * (x.numel() * frac + packed.numel() + n * M * (1 + (res is not None) + (mask is not None)
-                                                                     + ((mask_bits is not None) + (bits_out is not None)) / 32.0))
-        if stats is not None:
-            assert mask is None and mask_bits is None and bits_out is None and stats.is_contiguous() and stats.dtype == torch.float32
-            with PROFILE.span(span, 2.0 * n * M * K, tag, nbytes):
+    n = Nb * OH * OW
+    nbytes = 4.0 * (x.numel() + packed.numel() + n * M * (1 + (res is not None) + (mask is not None)
+                                                          + ((mask_bits is not None) + (bits_out is not None)) / 32.0))
+
+    def launch(span, schedule):
+        with PROFILE.span(span, 2.0 * n * M * K, tag, nbytes):
+            if stats is not None:
+                assert mask is None and mask_bits is None and bits_out is None and stats.is_contiguous() and stats.dtype == torch.float32
                 L.check(lib.dasac_conv_gemm_stats(x.data_ptr(), packed.data_ptr(), table.data_ptr(), out.data_ptr(), Nb, Cx, H, W, OH, OW,
                                                   stride, M, K, out.shape[2], out.shape[3], ostride, L.ptr(shift), L.ptr(res), int(relu),
-                                                  pix_begin, pix_count, schedule, L.ptr(ws), 0 if ws is None else ws.numel(),
+                                                  0, 0, schedule, L.ptr(ws), 0 if ws is None else ws.numel(),
                                                   stats.data_ptr(), L.stream_ptr()), "dasac_conv_gemm_stats")
-            return
-        with PROFILE.span(span, 2.0 * n * M * K, tag, nbytes):
-            L.check(fn(x.data_ptr(), packed.data_ptr(), table.data_ptr(), out.data_ptr(), Nb, Cx, H, W, OH, OW,
-                       stride, M, K, out.shape[2], out.shape[3], ostride, L.ptr(shift), L.ptr(res),
-                       L.ptr(mask), L.ptr(mask_bits), 0 if bits_out is None else bits_out.words.data_ptr(), int(relu),
-                       pix_begin, pix_count, schedule, L.ptr(ws), 0 if ws is None else ws.numel(),
-                       L.stream_ptr()), "dasac_conv_gemm")
+            else:
+                L.check(fn(x.data_ptr(), packed.data_ptr(), table.data_ptr(), out.data_ptr(), Nb, Cx, H, W, OH, OW,
+                           stride, M, K, out.shape[2], out.shape[3], ostride, L.ptr(shift), L.ptr(res),
+                           L.ptr(mask), L.ptr(mask_bits), 0 if bits_out is None else bits_out.words.data_ptr(), int(relu),
+                           0, 0, schedule, L.ptr(ws), 0 if ws is None else ws.numel(),
+                           L.stream_ptr()), "dasac_conv_gemm")
 
     if schedule is not None:
-        launch("conv_gemm<stream-K>" if schedule == 2 else "conv_gemm<tile-per-block>", 0, 0, int(schedule))
+        launch("conv_gemm<stream-K>" if schedule == 2 else "conv_gemm<tile-per-block>", int(schedule))
         return out
     if lib.dasac_conv_gemm_tail_split(Nb, OH, OW, M, K) > 0:
         # ONE launch: whole rounds one block per tile (lockstep over K: halo rows shared in L2) + the remaining tiles cut into
         # K-ranges that fill the chip once more (round 6; rounds 2-5 issued that remainder as a second, persistent stream-K launch)
-        launch("conv_gemm<tile+tail>", 0, 0, 0)
+        launch("conv_gemm<tile+tail>", 0)
         return out
     sk = PROFILE.on and lib.dasac_conv_gemm_schedule(Nb, OH, OW, M, K)
-    launch("conv_gemm<stream-K>" if sk else "conv_gemm<tile-per-block>", 0, 0, 0)
+    launch("conv_gemm<stream-K>" if sk else "conv_gemm<tile-per-block>", 0)
     return out
 
 
@@ -312,15 +315,12 @@ def conv_wgrad(spec, dz, x, weights, scale=None, dot=None, table=None, sum_dz=No
         fn = lib.dasac_conv_wgrad_x3 if PRECISION == "bf16x3" else lib.dasac_conv_wgrad
         L.check(fn(_c(dz).data_ptr(), x.data_ptr(), table.data_ptr(), Nb, Cx, H, W, OH, OW, spec.stride, M,
                    spec.K, ws.data_ptr(), ws.numel(), L.stream_ptr()), "dasac_conv_wgrad")
-    grads, tap0 = [], 0
-    for bi, (w, (kh, kw, _, _)) in enumerate(zip(weights, spec.branches)):
-        dw = _dest(None if outs is None else outs[bi], w)
+    grads = [_dest(None if outs is None else outs[bi], w) for bi, w in enumerate(weights)]
+    for w, dw, (taps, tap0) in zip(weights, grads, _branch_taps(spec)):
         L.check(lib.dasac_conv_wgrad_finish(ws.data_ptr(), Nb, OH, OW, M, spec.K, _c(w).data_ptr(), L.ptr(scale),
-                                            dw.data_ptr(), L.ptr(dot), L.ptr(sum_dz if tap0 == 0 else None), spec.cin, kh * kw,
+                                            dw.data_ptr(), L.ptr(dot), L.ptr(sum_dz if tap0 == 0 else None), spec.cin, taps,
                                             tap0, L.stream_ptr()),
                 "dasac_conv_wgrad_finish")
-        grads.append(dw)
-        tap0 += kh * kw
     return grads
 
 
@@ -893,11 +893,9 @@ class ExpandedConv:
         K = self.E if transposed else self.spec.cin
         if out is None:
             out = torch.empty((lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M)), dtype=torch.float32, device=weights[0].device)
-        tap0 = 0
-        for w, (kh, kw, _, _) in zip(weights, self.spec.branches):
-            L.check(lib.dasac_conv_pack_expanded(_c(w).data_ptr(), self.spec.cout, self.spec.cin, kh * kw, tap0, self.spec.taps,
+        for w, (taps, tap0) in zip(weights, _branch_taps(self.spec)):
+            L.check(lib.dasac_conv_pack_expanded(_c(w).data_ptr(), self.spec.cout, self.spec.cin, taps, tap0, self.spec.taps,
                                                  self.cp, int(transposed), out.data_ptr(), L.stream_ptr()), "dasac_conv_pack_expanded")
-            tap0 += kh * kw
         return _finish_pack(out, M, K)
 
     def forward(self, x, packed, table, bias):
@@ -929,14 +927,11 @@ class ExpandedConv:
             fn = lib.dasac_conv_wgrad_x3 if PRECISION == "bf16x3" else lib.dasac_conv_wgrad
             L.check(fn(d.data_ptr(), x.data_ptr(), table.data_ptr(), B, Cx, H, W, H, W, 1, self.E, self.spec.cin,
                        ws.data_ptr(), ws.numel(), L.stream_ptr()), "dasac_conv_wgrad")
-        grads, tap0 = [], 0
-        for bi, (w, (kh, kw, _, _)) in enumerate(zip(weights, self.spec.branches)):
-            dw = _dest(None if outs is None else outs[bi], w)
+        grads = [_dest(None if outs is None else outs[bi], w) for bi, w in enumerate(weights)]
+        for dw, (taps, tap0) in zip(grads, _branch_taps(self.spec)):
             L.check(lib.dasac_conv_wgrad_finish_expanded(ws.data_ptr(), B, H, W, self.E, self.spec.cin, dw.data_ptr(),
-                                                         self.spec.cout, kh * kw, tap0, self.cp, L.stream_ptr()),
+                                                         self.spec.cout, taps, tap0, self.cp, L.stream_ptr()),
                     "dasac_conv_wgrad_finish_expanded")
-            grads.append(dw)
-            tap0 += kh * kw
         return grads
 
     def dgrad(self, d, packed_t, table_t, in_hw, res=None, mask=None):

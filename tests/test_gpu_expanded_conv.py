@@ -131,7 +131,7 @@ def _expected_scatter(ex, dout):
 
 
 def _check_packs(ex, wd, ws, prec):
-    """Packing into a NaN-filled buffer and repacking new weights into that reused buffer (what Engine.packed_e does after an
+    """Packing into a NaN-filled buffer and repacking new weights into that reused buffer (what Engine.packed does after an
     optimiser step) give exactly a fresh pack; in fp32 the buffer is checked element by element, padding included."""
     from dasac_hip import lib as L
     lib = L.load()
@@ -275,14 +275,14 @@ def test_engine_rebuilds_expanded_packs_after_an_in_place_update():
     ops_e = [op for op in eng.plan.ops if op.kind == "conv" and op.expanded is not None]
     assert len(ops_e) == 1
     op = ops_e[0]
-    before = [eng.packed_e(op, tr).clone() for tr in (False, True)]
+    before = [eng.packed(op, tr).clone() for tr in (False, True)]
     with torch.no_grad():
         for c in op.convs:
             c.weight.mul_(1.01)
             c.bias.mul_(1.01)
     bb._logits(x).sum().backward()                           # forward and backward: both layouts are rebuilt
     for tr, old in zip((False, True), before):
-        got = eng._packs[(id(op), "e", tr)][1]
+        got = eng._packs[(id(op), tr)][1]
         fresh = op.expanded.pack([c.weight.detach() for c in op.convs], tr)
         assert torch.equal(got, fresh) and not torch.equal(got, old), tr
     with torch.no_grad():

@@ -58,6 +58,27 @@ def test_train_keeps_frozen_bn_in_eval_and_baseline_trains_bn():
     assert all(m.training for m in base.backbone.modules() if isinstance(m, nn.SyncBatchNorm))
 
 
+@pytest.mark.parametrize("arch", ["deeplabv2_resnet101", "fcn_vgg16_bn"])
+def test_conv_parameter_index_groups_restate_owners(arch):
+    """The named index groups of every conv op (weights, biases, BN affine), concatenated, are `op.pidx`, and every index
+    points at the parameter `owners()` names at that position -- what the backward pass reads instead of slicing `pidx`."""
+    import models
+    from dasac_hip import engine as E
+    net = models.get_model(_cfg(ARCH=arch), 0, num_classes=19, criterion=CRIT)
+    eng = E.Engine(net.backbone._plan())
+    convs = [op for op in eng.plan.ops if op.kind == "conv"]
+    assert len(convs) > 10 and sum(len(op.pidx) for op in convs) == len(eng.params)
+    same = lambda idx, owners: len(idx) == len(owners) and all(eng.params[j] is getattr(m, a) for j, (m, a) in zip(idx, owners))
+    for op in convs:
+        assert op.w_idx + op.b_idx + op.bn_idx == op.pidx
+        assert same(op.pidx, op.owners())
+        assert same(op.w_idx, [(c, "weight") for c in op.convs])
+        assert same(op.b_idx, [(c, "bias") for c in op.convs if c.bias is not None])
+        assert same(op.bn_idx, [] if op.bn is None else [(op.bn, "weight"), (op.bn, "bias")])
+    if arch == "deeplabv2_resnet101":
+        assert any(len(op.convs) > 1 and len(op.b_idx) == len(op.convs) for op in convs)      # the ASPP classifier: one bias per branch
+
+
 def test_no_cpu_fallback_and_criterion_check():
     import models
     from dasac_hip import DasacError
