@@ -972,3 +972,43 @@ def label_hist(labels_u8, counts=None):
             B, counts.dtype, tuple(counts.shape)))
     L.check(lib.dasac_label_hist(labels_u8.data_ptr(), B, HW, counts.data_ptr(), L.stream_ptr()), "dasac_label_hist")
     return counts
+
+
+MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS = 4, 2
+
+
+def mask_counts(scores, label_maps, gt, counts=None, ignore_index=255, num_classes=None):
+    """Validation counts of several mask layers against one ground truth in ONE launch (train.py:386-399, utils/metrics.py:18-39).
+    scores: up to 4 fp32 [B,C,H,W] tensors (arg-max, first maximum wins); label_maps: up to 2 int64 [B,H,W] maps (255 = no label);
+    gt int64 [B,H,W].  Accumulates (tp, fp, fn) per layer into `counts` (int64 [L,3,C], scores first, then label maps; allocated
+    zeroed when None) and returns it.  With label maps only, C comes from `counts` or `num_classes`."""
+    lib = L.load()
+    scores, label_maps = list(scores or ()), list(label_maps or ())
+    L.require_gpu(gt, counts, *scores, *label_maps)
+    n_layers = len(scores) + len(label_maps)
+    if n_layers == 0 or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
+        raise L.DasacError("mask_counts takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
+            MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
+    if gt.dtype != torch.int64 or gt.dim() != 3:
+        raise L.DasacError("mask_counts: gt must be int64 [B,H,W] (got {} {})".format(gt.dtype, tuple(gt.shape)))
+    B, H, W = gt.shape
+    Cn = scores[0].shape[1] if scores else (counts.shape[2] if counts is not None else num_classes)
+    if Cn is None:
+        raise L.DasacError("mask_counts: label maps alone do not tell the class count; pass counts or num_classes")
+    for s in scores:
+        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
+            raise L.DasacError("mask_counts: a score tensor must be float32 {} (got {} {})".format((B, Cn, H, W), s.dtype, tuple(s.shape)))
+    for m in label_maps:
+        if m.dtype != torch.int64 or tuple(m.shape) != (B, H, W):
+            raise L.DasacError("mask_counts: a label map must be int64 {} (got {} {})".format((B, H, W), m.dtype, tuple(m.shape)))
+    if counts is None:
+        counts = torch.zeros((n_layers, 3, Cn), dtype=torch.int64, device=gt.device)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (n_layers, 3, Cn) or not counts.is_contiguous():
+        raise L.DasacError("mask_counts accumulates into a contiguous int64 [{},3,{}] tensor (got {} {})".format(
+            n_layers, Cn, counts.dtype, tuple(counts.shape)))
+    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
+    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
+    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
+    L.check(lib.dasac_mask_counts(*sp, *mp, gt.data_ptr(), B, Cn, H * W, int(ignore_index), counts.data_ptr(), L.stream_ptr()),
+            "dasac_mask_counts")
+    return counts

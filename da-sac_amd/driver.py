@@ -424,3 +424,121 @@ def compute_sample_weights(net, batches, num_images, lut=None, teacher=False):
         table = table.cpu()
     dist.all_reduce(table)
     return table.cpu()
+
+
+# --------------------------------------------------------------------------------------------------
+# reference-form validation (train.py:339-469): student and teacher IoU, loss means, checkpoint score
+# --------------------------------------------------------------------------------------------------
+VALIDATION_SCORE_LAYERS = ("logits_up", "teacher_init", "teacher_refined")      # through argmax(., 1), train.py:394-395
+VALIDATION_LABEL_LAYERS = ("teacher_labels",)                                   # label maps as they are, 255 = no label (:396-397)
+
+
+def validation_batches(loader, max_iter=None):
+    """The batches `Trainer.validation` evaluates (train.py:347-348,375,405-406): `max_iter` defaults to len(loader), and the
+    loop leaves on `n > max_iter` AFTER it has processed batch n -- a longer loader contributes max_iter + 2 batches."""
+    if max_iter is None and hasattr(loader, "__len__"):
+        max_iter = len(loader)
+    for n, batch in enumerate(loader):
+        yield batch
+        if max_iter is not None and n > max_iter:
+            break
+
+
+def stat_mean(values):
+    """`StatManager.update_stats` + `summarize_key` (utils/stat_manager.py:40-61) over one key's values: python-float sum
+    divided by the count, and 0 when there is no value or the sum is exactly 0."""
+    total = 0.0
+    for v in values:
+        total += v
+    return total / len(values) if len(values) > 0 and abs(total) > 0. else 0
+
+
+def class_subset_mean(values, ignore_classes=()):
+    """train.py:370-371,447-460: float32 mean over the classes NOT listed in VAL.IGNORE_CLASS."""
+    ignore = set(int(i) for i in ignore_classes)
+    return torch.Tensor([float(v) for i, v in enumerate(values) if i not in ignore]).mean().item()
+
+
+def summarise_validation(counts, ignore_classes=()):
+    """counts {layer: int64 [3,C]} -> (per_class {layer: (jaccard, precision, recall)}, mean {layer: (mIoU, precision,
+    recall)} over the kept classes, checkpoint_score = max over layers of mIoU, starting from 0.0: train.py:408,430-464)."""
+    per_class, mean, score = {}, {}, 0.0
+    for layer, table in counts.items():
+        per_class[layer] = summarise_iou(table)
+        mean[layer] = tuple(class_subset_mean(v, ignore_classes) for v in per_class[layer])
+        score = max(mean[layer][0], score)
+    return per_class, mean, score
+
+
+def validation(net, loader, step="source", group_size=None, max_iter=None, ignore_classes=(), num_classes=19, num_groups=None):
+    """`Trainer.validation` (train.py:339-469) with its step function (`step` :119-155 or `_step_target` :211-250, train=False):
+    eval mode under no_grad (the previous mode is restored), loss means, one (tp, fp, fn) table per mask layer, the per-class and
+    class-subset summaries and the checkpoint score.  Neither the teacher nor the class prior is updated.
+
+      step="source": batches (image, gt); `net(image, gt)`; the layer is `logits_up`; losses are THIS rank's `val.mean()`
+                     (train.py:147-151, no reduction over ranks).  A baseline net validates its target set this way (:113-115).
+      step="target": batches (frames1, frames_gt, frames2, affine, affine_inv) as loaded, [N,T,...] each, through `prep_batch`
+                     (`num_groups` defaults to loaded groups x world); `net(f1, gt, f2, affine, affine_inv, use_teacher=True,
+                     update_teacher=False, T=group_size)`; layers `logits_up`, `teacher_init`, `teacher_refined` (arg-max) and
+                     `teacher_labels` (as it is) against the frames_gt the forward pass has rewritten from -1 to 255; losses are
+                     averaged over ranks (:243-246: fp32 sum over ranks / world per batch -- here ONE collective over the
+                     [batches, keys] matrix after the loop, the same arithmetic as `reduce_losses`; every rank must see the
+                     same number of batches, as in the reference).
+
+    All layers of a batch go through ONE `ops.mask_counts` launch into one device table; nothing in the loop waits for the
+    device beyond what the forward pass does; one D2H copy at the end.  With a process group of world > 1 the tables are summed
+    over ranks (gloo: the HOST table, see compute_sample_weights; RCCL: on the device).  `max_iter`: see validation_batches.
+    Loss means follow StatManager (stat_mean).  Returns a namespace: losses {key: mean}, counts {layer: int64 [3,C]}, per_class
+    {layer: (jaccard, precision, recall)}, mean {layer: (mIoU, precision, recall)} over the classes not in `ignore_classes`,
+    checkpoint_score = max over layers of mIoU.  The reference computes the score on its main process only and returns 0.0
+    elsewhere; here EVERY rank returns the same value (each holds the summed counts) -- save on rank 0 only as before.
+    Not reproduced: metrics.py:30 overwrites the prediction in place at ignored pixels (nothing reads it afterwards), and the
+    reference's float32 counters, which stop being exact past 2^24 pixels per class -- the counts here are exact int64."""
+    from types import SimpleNamespace
+    import torch.distributed as dist
+    from dasac_hip import ops
+    assert step in ("source", "target"), step
+    core = net.module if hasattr(net, "module") else net
+    device = next(core.parameters()).device
+    rank, world = _dist_state(None, None)
+    was = core.training
+    core.eval()
+    layers, table, rows, keys = None, None, [], None
+    try:
+        with torch.no_grad():
+            for batch in validation_batches(loader, max_iter):
+                if step == "source":
+                    image, gt = (t.to(device, non_blocking=True) for t in batch)
+                    losses, outs = net(image, gt)
+                else:
+                    groups = num_groups if num_groups is not None else batch[0].shape[0] * world
+                    f1, gt, f2, affine, affine_inv = (prep_batch(t, groups, group_size, device=device) for t in batch)
+                    losses, outs = net(f1, gt, f2, affine, affine_inv, use_teacher=True, update_teacher=False, T=group_size)
+                gt = gt.view(-1, *gt.shape[-2:])
+                if layers is None:
+                    layers = ([k for k in VALIDATION_SCORE_LAYERS if k in outs], [k for k in VALIDATION_LABEL_LAYERS if k in outs])
+                    keys = sorted(losses)
+                scores, maps = [outs[k] for k in layers[0]], [outs[k] for k in layers[1]]
+                table = ops.mask_counts(scores, maps, gt, table, num_classes=num_classes)
+                rows.append(torch.cat([losses[k].detach().mean().reshape(1) for k in keys]))
+    finally:
+        core.train(was)
+    if table is None:
+        return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0)
+    names = layers[0] + layers[1]
+    loss_rows = torch.stack(rows)
+    multi = dist.is_available() and dist.is_initialized() and world > 1
+    if multi:
+        # gloo moves device tensors with no ordering against the stream that fills them (see prep_batch): the HOST tables are
+        # summed; RCCL sums on the device, stream-ordered, before the one D2H copy.
+        if dist.get_backend() == "gloo":
+            table, loss_rows = table.cpu(), loss_rows.cpu()
+        dist.all_reduce(table)
+        if step == "target":
+            dist.all_reduce(loss_rows)
+            loss_rows = loss_rows / world
+    table, loss_rows = table.cpu(), loss_rows.cpu().tolist()
+    counts = {name: table[i] for i, name in enumerate(names)}
+    per_class, mean, score = summarise_validation(counts, ignore_classes)
+    losses = {k: stat_mean([row[i] for row in loss_rows]) for i, k in enumerate(keys)}
+    return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score)

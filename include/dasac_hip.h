@@ -391,6 +391,20 @@ int dasac_dropout_planes(uint64_t seed, uint64_t offset, float p, int64_t planes
 int dasac_iou_counts(const float* logits, const int64_t* gt, int B, int C, int64_t HW, int ignore_index,
                      int64_t* counts, dasac_stream_t stream);
 
+/* Validation counts of several mask layers against ONE ground-truth map in one launch (train.py:386-399: one `Jaccard` per
+ * layer -- `logits_up`, `teacher_init`, `teacher_refined` through argmax(., 1), `teacher_labels` as it is; utils/metrics.py:18-39
+ * `Jaccard.add_sample`).  Up to 4 score tensors fp32 [B,C,HW] (arg-max, first maximum wins) and up to 2 label maps int64
+ * [B,HW]; any of the six may be NULL, at least one is not.  The layers are numbered in argument order over the non-NULL
+ * pointers, scores first, then label maps.  counts: int64 [L][3][C] = (tp, fp, fn) per layer, ACCUMULATED into (the caller zeroes
+ * it once per evaluation and sums it over ranks).  Per pixel: gt == ignore_index is skipped; p == gt adds tp[gt]; otherwise
+ * fp[p] if 0 <= p < C and fn[gt] if 0 <= gt < C (a label of 255 over a labelled pixel is a false negative only, gt == -1 a
+ * false positive only, as in dasac_iou_counts).  Integer adds only: exact and bit-identical from run to run -- the reference's
+ * float32 counters (exact up to 2^24 pixels per class) are not reproduced.  C <= 64.  The ground truth is read once for all
+ * layers; no load leaves a buffer (H*W needs no alignment, pointers only that of their element type).  No workspace. */
+int dasac_mask_counts(const float* scores0, const float* scores1, const float* scores2, const float* scores3,
+                      const int64_t* labels0, const int64_t* labels1, const int64_t* gt, int B, int C, int64_t HW,
+                      int ignore_index, int64_t* counts, dasac_stream_t stream);
+
 /* Per-image class statistics for importance-sampled target selection (tools/compute_IS_weights.py:58-83, on the device):
  * counts[b][v] += number of pixels of image b with value v, v in 0..255 (value 255 is counted too; callers drop it).
  * labels: [B][HW] uint8, any alignment (an unaligned head and a tail of any length per image are read byte by byte, the

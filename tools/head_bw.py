@@ -34,9 +34,9 @@ ONLY = os.environ.get("HEAD_BW_ONLY", "")        # substring filter (tools/head_
 rows = []
 
 
-def row(name, nbytes, fn):
+def row(name, nbytes, fn, iters=10):
     if ONLY in name:
-        rows.append((name, nbytes, timeit(fn)))
+        rows.append((name, nbytes, timeit(fn, iters)))
 
 
 row("upsample_softmax (logits_up)", T, lambda: ops.upsample_softmax(low, (H, H)))
@@ -83,6 +83,24 @@ ph = tvp.sample_photometric()
 # u8 views in (3 B), fp32 frames out (12 B) per view pixel; the blur's two box passes and the jitter chain stay in the workspace
 row("view_photometric (blur + jitter, 4 views)", Lv * Hc * Wc * 15, lambda: tvp.augment(u8, gtv, ph))
 row("iou_counts (argmax + tp/fp/fn)", T + P * 8, lambda: ops.iou_counts(up, y))
+# validation counts of several layers in one launch (profiles/mask_counts_bw.md): one score layer against iou_counts above; three
+# score layers + one label map against three iou_counts launches + the cheapest ATen count of a label map (bincount of 3*C keys)
+row("mask_counts (1 score layer)", T + P * 8, lambda: ops.mask_counts([up], [], y), 200)
+up2 = up.clone()
+lab64 = torch.where(ign, torch.full_like(y, 255), up.argmax(1))
+row("mask_counts (3 score layers + 1 label map)", 3 * T + P * 16, lambda: ops.mask_counts([up, probs, up2], [lab64], y), 200)
+
+
+def aten_label_counts(pred, gt, nc=C):
+    keep = gt != 255
+    p, g = pred[keep], gt[keep]
+    hit = p == g
+    key = torch.cat([g[hit], nc + p[~hit & (p < nc)], 2 * nc + g[~hit]])
+    return torch.bincount(key, minlength=3 * nc)
+
+
+row("ATen label-map counts (mask + bincount)", P * 16, lambda: aten_label_counts(lab64, y), 50)
+row("iou_counts, 200 launches per window", T + P * 8, lambda: ops.iou_counts(up, y), 200)
 lut = torch.tensor(driver.CITYSCAPES_TRAIN_TO_ID, dtype=torch.uint8, device="cuda")
 row("infer_labels (upsample+softmax+argmax+LUT)", low.numel() * 4 + P, lambda: ops.infer_labels(low, (H, H), lut))
 # ResNet-101 DeepLabv2 parameter set: 43.9 M floats = 175.6 MB.  SGD: p, g read, momentum read + written, p written;
