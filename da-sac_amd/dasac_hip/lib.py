@@ -90,7 +90,15 @@ PROTOTYPES = {
     "dasac_crop_table_ints": (_i, [_i, _i]),
     "dasac_resize_u8": (_i, [_p, _l, _p, _l, _i, _p, _p, _l, _i, _p, _l, _p, _l, _p]),
     "dasac_make_crops": (_i, [_p, _l, _p, _l, _i, _p, _p, _l, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "dasac_vis_panels": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "dasac_vis_grid": (_i, [_p, _i, _i, _i, _i, _f, _p, _p]),
 }
+
+
+class VisJob(C.Structure):
+    """`dasac_vis_job` of include/dasac_hip.h (48 bytes)."""
+    _fields_ = [("src", _p), ("backdrop", _p), ("kind", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("softmax", C.c_int32), ("column", C.c_int32), ("column2", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DasacError(RuntimeError):

@@ -1012,3 +1012,74 @@ def mask_counts(scores, label_maps, gt, counts=None, ignore_index=255, num_class
     L.check(lib.dasac_mask_counts(*sp, *mp, gt.data_ptr(), B, Cn, H * W, int(ignore_index), counts.data_ptr(), L.stream_ptr()),
             "dasac_mask_counts")
     return counts
+
+
+VIS_IMAGE, VIS_LABELS, VIS_SCORES, VIS_CONF = 0, 1, 2, 3
+
+
+def vis_panels(jobs, size, panels, mean, std, palette, cmap, want_u8=False):
+    """The epoch summary panels of one batch in ONE launch (base_trainer.py:75-198; include/dasac_hip.h: dasac_vis_panels).
+    jobs: sequence of (kind, src, backdrop, softmax, column, column2) with kind one of VIS_IMAGE (src f32 [B,3,H,W]), VIS_LABELS
+    (src i64 [B,H,W]), VIS_SCORES (src f32 [B,C,H,W]; class overlay to `column`, confidence overlay to `column2`), VIS_CONF (src f32
+    [B,H,W] or [B,1,H,W]); backdrop f32 [B,3,H,W] of the source's H x W (None for VIS_IMAGE).  size = (h, w) of one panel, `panels`
+    the number of panel columns P.  palette u8 [256,3] and cmap f32 [256,3] on the device; mean / std three floats.  Returns the
+    strip f32 [B,3,h,P*w], and with want_u8 also the quantised rows u8 [B,3,h,P*w].  No input is written."""
+    import ctypes as C
+    lib = L.load()
+    jobs = list(jobs)
+    if not jobs:
+        raise L.DasacError("vis_panels: no job")
+    L.require_gpu(palette, cmap, *[t for job in jobs for t in job[1:3]])
+    h, w = int(size[0]), int(size[1])
+    P = int(panels)
+    if palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or cmap.dtype != torch.float32 or tuple(cmap.shape) != (256, 3):
+        raise L.DasacError("vis_panels: palette must be uint8 [256,3] and cmap float32 [256,3] (got {} {} and {} {})".format(
+            palette.dtype, tuple(palette.shape), cmap.dtype, tuple(cmap.shape)))
+    B = jobs[0][1].shape[0]
+    table, keep, used = (L.VisJob * len(jobs))(), [_c(palette), _c(cmap)], set()
+    for i, (kind, src, back, softmax, column, column2) in enumerate(jobs):
+        want = {VIS_IMAGE: (torch.float32, 4), VIS_LABELS: (torch.int64, 3), VIS_SCORES: (torch.float32, 4), VIS_CONF: (torch.float32, 3)}.get(kind)
+        if want is None:
+            raise L.DasacError("vis_panels: job {}: unknown kind {}".format(i, kind))
+        if kind == VIS_CONF and src.dim() == 4 and src.shape[1] == 1:
+            src = src[:, 0]
+        if src.dtype != want[0] or src.dim() != want[1] or src.shape[0] != B or (kind == VIS_IMAGE and src.shape[1] != 3):
+            raise L.DasacError("vis_panels: job {} (kind {}): bad source {} {}".format(i, kind, src.dtype, tuple(src.shape)))
+        H, W = src.shape[-2:]
+        if kind != VIS_IMAGE and (back is None or back.dtype != torch.float32 or tuple(back.shape) != (B, 3, H, W)):
+            raise L.DasacError("vis_panels: job {}: the backdrop must be float32 {} (got {})".format(
+                i, (B, 3, H, W), None if back is None else (back.dtype, tuple(back.shape))))
+        cols = [int(column)] + ([int(column2)] if kind == VIS_SCORES else [])
+        if len(set(cols)) != len(cols) or any(c < 0 or c >= P or c in used for c in cols):
+            raise L.DasacError("vis_panels: job {}: columns {} outside 0..{} or already taken".format(i, cols, P - 1))
+        used.update(cols)
+        src, back = _c(src), (None if kind == VIS_IMAGE else _c(back))
+        keep += [src, back]
+        table[i] = L.VisJob(src.data_ptr(), L.ptr(back), kind, src.shape[1] if kind == VIS_SCORES else 1, H, W, int(bool(softmax)),
+                            cols[0], cols[-1] if kind == VIS_SCORES else 0, 0)
+    if len(used) != P:
+        raise L.DasacError("vis_panels: {} of {} panel columns are written by no job".format(P - len(used), P))
+    device = keep[0].device
+    jobs_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+    strip = torch.empty((B, 3, h, P * w), dtype=torch.float32, device=device)
+    rows = torch.empty((B, 3, h, P * w), dtype=torch.uint8, device=device) if want_u8 else None
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    L.check(lib.dasac_vis_panels(jobs_dev.data_ptr(), C.cast(table, C.c_void_p), len(jobs), B, h, w, P, C.cast(m3, C.c_void_p),
+                                 C.cast(s3, C.c_void_p), keep[0].data_ptr(), keep[1].data_ptr(), strip.data_ptr(), L.ptr(rows),
+                                 L.stream_ptr()), "dasac_vis_panels")
+    return (strip, rows) if want_u8 else strip
+
+
+def vis_grid(strip, padding=8, pad_value=0.9):
+    """`_visualise_grid` (base_trainer.py:258-270) of a float strip [B,3,h,W]: quantised with `.mul(255).clamp(0, 255).byte()` and
+    stacked like make_grid(nrow=1, padding, pad_value): u8 [3, B*(h+padding)+padding, W+padding], a single row [3,h,W]."""
+    lib = L.load()
+    L.require_gpu(strip)
+    if strip.dtype != torch.float32 or strip.dim() != 4 or strip.shape[1] != 3:
+        raise L.DasacError("vis_grid takes a float32 [B,3,h,W] strip (got {} {})".format(strip.dtype, tuple(strip.shape)))
+    strip = _c(strip)
+    B, _, h, wt = strip.shape
+    pad = int(padding) if B > 1 else 0
+    grid = torch.empty((3, B * (h + pad) + pad, wt + pad), dtype=torch.uint8, device=strip.device)
+    L.check(lib.dasac_vis_grid(strip.data_ptr(), B, h, wt, int(padding), float(pad_value), grid.data_ptr(), L.stream_ptr()), "dasac_vis_grid")
+    return grid

@@ -542,3 +542,59 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     per_class, mean, score = summarise_validation(counts, ignore_classes)
     losses = {k: stat_mean([row[i] for row in loss_rows]) for i, k in enumerate(keys)}
     return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score)
+
+
+# --------------------------------------------------------------------------------------------------
+# epoch summaries (base_trainer.py:75-218,272-278): the panel strip of the fixed batches, rendered on the device
+# --------------------------------------------------------------------------------------------------
+from visualise import FixedBatches  # noqa: E402,F401  (`save_fixed_batch` / `has_fixed_batch`, base_trainer.py:200-218)
+
+
+def visualise_results(net, batch, step="source", group_size=None, im_size=(256, 256), num_groups=None, palette=None, cmap=None,
+                      mean=None, std=None):
+    """`BaseTrainer.visualise_results` -> `step(..., train=False, visualise=True)` (base_trainer.py:272-278, train.py:140-141,
+    235-236) for one fixed batch: eval mode under no_grad (the previous mode is restored), neither the teacher nor the class prior
+    is updated (the contract of `validation`).
+
+      step="source": batch (image, gt) -> `net(image, gt)` -> panels image, ground truth, prediction, confidence;
+      step="target": batch (frames1, frames_gt, frames2, affine, affine_inv) as loaded, [N,T,...] each, through `prep_batch`
+                     (`num_groups` defaults to loaded groups x world) -> `net(f1, gt, f2, affine, affine_inv, use_teacher=True,
+                     update_teacher=False, T=group_size)` -> all thirteen panels, frames2 as `image2`.
+
+    The panels are rendered by ONE kernel launch where the tensors are (visualise.render); the u8 rows -- not `net_outs` -- are
+    gathered over the ranks, rank-major (visualise.gather_rows: host tensors under gloo), and stacked into the grid
+    (visualise.to_grid).  Returns a namespace: grid u8 [3, rows, cols] on the HOST with every rank's rows (on every rank),
+    names = the panel names in strip order, running_conf = the class prior as the reference logs it (list of C floats, None for
+    the source step).  Writing stays the caller's: `writer.add_image(tag, grid, epoch, dataformats="CHW")` and
+    `writer.add_scalar("running_conf/%02d" % i, conf, epoch)`."""
+    from types import SimpleNamespace
+    import visualise as V
+    assert step in ("source", "target"), step
+    core = net.module if hasattr(net, "module") else net
+    device = next(core.parameters()).device
+    _, world = _dist_state(None, None)
+    kw = dict(im_size=im_size, palette=palette, cmap=cmap, mean=V.MEAN if mean is None else mean, std=V.STD if std is None else std,
+              want_u8=True)
+    was = core.training
+    core.eval()
+    try:
+        with torch.no_grad():
+            if step == "source":
+                image, gt = (t.to(device, non_blocking=True) for t in batch[:2])
+                if gt.device == batch[1].device:
+                    gt = gt.clone()                 # the forward pass rewrites -1 to 255 in place: not in the caller's batch
+                _, outs = net(image, gt)
+                image2 = None
+            else:
+                groups = num_groups if num_groups is not None else batch[0].shape[0] * world
+                image, gt, image2, affine, affine_inv = (prep_batch(t, groups, group_size, device=device) for t in batch)
+                if gt.device == batch[1].device:
+                    gt = gt.clone()
+                _, outs = net(image, gt, image2, affine, affine_inv, use_teacher=True, update_teacher=False, T=group_size)
+            gt = gt.view(-1, *gt.shape[-2:])
+            names = V.panel_names(outs, image2)
+            _, rows = V.render(image, gt, outs, image2=image2, **kw)
+    finally:
+        core.train(was)
+    rows, confs = V.gather_rows(rows, outs.get("running_conf"))
+    return SimpleNamespace(grid=V.to_grid(rows.cpu()), names=names, running_conf=confs)

@@ -477,6 +477,38 @@ int dasac_make_crops(const uint8_t* images, int64_t images_bytes, const uint8_t*
                      const float* std3, int ignore_label, float* frames, int64_t* labels_out, uint8_t* image_u8,
                      uint8_t* label_u8, uint8_t* mask_u8, dasac_stream_t stream);
 
+/* The trainer's epoch summary panels (base_trainer.py:75-198 `BaseTrainer._visualise`; helpers `_apply_cmap` :228-248,
+ * `_error_rgb` :250-256, `_visualise_grid` :258-270), rendered on the device: ONE launch renders every panel of every image of
+ * a batch into the strip float32 [B,3,h,P*w] (the reference's `visuals`, panel p in columns [p*w, (p+1)*w)) and, when rows_u8
+ * is not NULL, into u8 [B,3,h,P*w] = trunc(clamp(255 * strip, 0, 255)) (:264).  `jobs`: DEVICE array of n_jobs records,
+ * `jobs_host` the same records on the HOST (the arguments are checked on it).  Per job, by `kind`:
+ *   DASAC_VIS_IMAGE   src f32 [B,3,H,W]: downsize(src * std + mean)                                             (:119,:148,:172)
+ *   DASAC_VIS_LABELS  src i64 [B,H,W]: values saturated to 0..255 -> palette at the four taps -> / 255 -> downsize (:123-131)
+ *   DASAC_VIS_SCORES  src f32 [B,C,H,W]: softmax over C at each tap when `softmax`, every class resized, max / FIRST arg-max;
+ *                     the class colours go to `column`, inferno(1 - max) to `column2`                      (:134-145,:152-165)
+ *   DASAC_VIS_CONF    src f32 [B,H,W]: inferno(1 - downsize(src))                                                 (:179-183)
+ * downsize = bilinear, align_corners=True (:99-109), shrinking or enlarging, any H x W, output extent 1 included.  Every kind
+ * but IMAGE is blended: 0.3 * downsize(backdrop * std + mean) + 0.7 * colours, backdrop f32 [B,3,H,W] of the job's H x W.
+ * palette: DEVICE u8 [256][3]; cmap: DEVICE f32 [256][3], indexed by trunc(256 * v) clipped to 0..255; mean3 / std3: HOST
+ * arrays of 3 floats.  Every tap index is clamped inside its plane: no load leaves a tensor of the stated shape.
+ * dasac_vis_grid: torchvision's make_grid(nrow=1, padding, pad_value) of the quantised rows (:269): for B > 1 u8
+ * [3][B*(h+padding)+padding][wt+padding] filled with trunc(255 * pad_value), row k at y = k*(h+padding)+padding, x = padding;
+ * for B == 1 the row itself, [3][h][wt].  strip f32 [B,3,h,wt]. */
+#define DASAC_VIS_IMAGE 0
+#define DASAC_VIS_LABELS 1
+#define DASAC_VIS_SCORES 2
+#define DASAC_VIS_CONF 3
+typedef struct dasac_vis_job {
+  const void* src;
+  const float* backdrop; /* NULL for DASAC_VIS_IMAGE */
+  int32_t kind, C, H, W, softmax, column, column2, reserved;
+} dasac_vis_job;
+int dasac_vis_panels(const dasac_vis_job* jobs, const dasac_vis_job* jobs_host, int n_jobs, int B, int h, int w, int P,
+                     const float* mean3, const float* std3, const uint8_t* palette, const float* cmap, float* strip,
+                     uint8_t* rows_u8, dasac_stream_t stream);
+int dasac_vis_grid(const float* strip, int B, int h, int wt, int padding, float pad_value, uint8_t* grid,
+                   dasac_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
