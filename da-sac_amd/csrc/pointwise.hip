@@ -397,9 +397,11 @@ __global__ void ema_finish(const double* __restrict__ sq, int n, float* __restri
   if (threadIdx.x == 0) out[0] = (float)s;
 }
 
-// ---- torch.optim.SGD(momentum, dampening 0, no nesterov) over every parameter in one launch ---------
+// ---- torch.optim.SGD(momentum, dampening 0, nesterov or not) over every parameter in one launch ---------
 // (base_trainer.py:63-66 builds it over the four groups of basenet.py:73-95; per-group lr / weight decay)
 //   d = g (+ g2) + wd*p ;  buf = first ? d : momentum*buf + d ;  p = p - lr*buf        (same op order as ATen)
+// NESTEROV (OPT_NESTEROV, base_trainer.py:64): p = p - lr*(d + momentum*buf) -- torch/optim/sgd.py:462-473,
+// `_foreach_add_(grads, bufs, alpha=momentum)` then `_foreach_add_(params, grads, alpha=-lr)`, each `x + alpha*y` one fma.
 // g2 (optional): a second gradient of the same parameter -- the source-pass gradient the driver set aside while the target
 // pass ran (train.py accumulates both into .grad: one `add_` launch per parameter, 320 per step; here the sum happens in
 // the update itself, g2 + g in AccumulateGrad's operand order, so the result is bit-identical).
@@ -415,6 +417,15 @@ struct SgdGroups {
   float lr[8], wd[8];
 };
 
+// a*b + c as ATen's foreach kernels compute it: they are built with fp contraction, so every `x + alpha*y` of theirs is ONE fma
+// (tools/aten_contraction_probe.py: 2^20 elements per op, no element differs from the fma form; profiles/fused_optim.md).
+// This file is built with contraction off: the plain-momentum kernel keeps the two roundings it has always had.
+template <bool FMA>
+__device__ __forceinline__ float mul_add(float a, float b, float c) {
+  return FMA ? __fmaf_rn(a, b, c) : a * b + c;
+}
+
+template <bool NESTEROV>
 __global__ __launch_bounds__(256) void sgd_chunks(const SgdTensor* __restrict__ tensors, const int2* __restrict__ chunks,
                                                   SgdGroups hp, float momentum, int first) {
   const int2 ch = chunks[blockIdx.x];
@@ -428,14 +439,110 @@ __global__ __launch_bounds__(256) void sgd_chunks(const SgdTensor* __restrict__ 
       const float p = t.p[i];
       float d = t.g[i];
       if (t.g2) d = t.g2[i] + d;
-      if (wd != 0.f) d = d + wd * p;
+      if (wd != 0.f) d = mul_add<NESTEROV>(wd, p, d);
       float b = d;
       if (!first) {
         b = t.buf[i] * momentum;
         b = b + d;
       }
       t.buf[i] = b;
-      t.p[i] = p - lr * b;
+      if (NESTEROV) b = mul_add<true>(momentum, b, d);      // sgd.py:462-465, grad.add(buf, alpha=momentum)
+      t.p[i] = mul_add<NESTEROV>(-lr, b, p);
+    }
+  }
+}
+
+// ---- torch.optim.Adam (L2 weight decay in the gradient, no amsgrad / maximize) over every parameter in one launch ---------
+// (base_trainer.py:57-61: Adam(groups, lr, betas=(BETA1, 0.999), weight_decay); core/config.py:135-140 ships BETA1 = 0.5).
+// Operation order of torch/optim/adam.py, _multi_tensor_adam, the non-capturable, non-amsgrad path (torch 2.10):
+//   :698-700  g = g + wd*p                      _foreach_add(grads, params, alpha=weight_decay), only if wd != 0
+//   :705-707  m = lerp(m, g, 1 - beta1)         _foreach_lerp_; ATen/native/Lerp.h:32-34 picks the formula by |w| < 0.5:
+//                                               m + w*(g - m)   or   g - (g - m)*(1 - w)    (BETA1 = 0.5 takes the second)
+//   :709      v = v*beta2                       _foreach_mul_
+//   :722-724  v = v + (1 - beta2)*(g*g)         _foreach_addcmul_: a + value*(b*c)
+//   :772-781  step_size = lr/(1 - beta1^step), bc2_sqrt = (1 - beta2^step)^0.5: python doubles, per tensor (HOST side)
+//   :791-794  den = sqrt(v); den = den/bc2_sqrt; den = den + eps
+//   :795-800  p = p + (-step_size)*(m/den)      _foreach_addcdiv_: a + value*(b/c)
+// with every scalar rounded to fp32 once (the foreach functors' opmath type) and every `a + s*x` above one fma, as ATen's
+// kernels contract it (mul_add<true>; the separate _foreach_mul_ / sqrt / div / add passes round on their own).  This file is
+// compiled without fast-math: `/` and sqrtf are the correctly rounded ones.  g2 as for sgd_chunks.
+struct AdamTensor {
+  float* p;
+  const float* g;
+  const float* g2;
+  float* m;
+  float* v;
+  int64_t n;
+  int32_t group;
+  int32_t reserved;
+  float step_size;
+  float bc2_sqrt;
+};
+static_assert(sizeof(AdamTensor) == 64, "AdamTensor is 8 x 8 bytes (dasac_hip/optim.py builds it as int64 rows)");
+struct AdamGroups {
+  float wd[8];
+};
+struct AdamScalars {
+  float w1, one_minus_w1, beta2, w2, eps;      // w1 = 1 - beta1, w2 = 1 - beta2 (rounded from the double difference)
+};
+
+__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float wd, float neg_step, float bc2_sqrt,
+                                             const AdamScalars& s, bool small_w) {
+  if (wd != 0.f) g = mul_add<true>(wd, p, g);
+  const float diff = g - m;
+  m = small_w ? mul_add<true>(s.w1, diff, m) : mul_add<true>(-diff, s.one_minus_w1, g);
+  v = v * s.beta2;
+  v = mul_add<true>(s.w2, g * g, v);
+  float den = sqrtf(v);
+  den = den / bc2_sqrt;
+  den = den + s.eps;
+  p = mul_add<true>(neg_step, m / den, p);
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));      // 16-byte aligned: one global_load/store_dwordx4
+__global__ __launch_bounds__(256) void adam_chunks(const AdamTensor* __restrict__ tensors, const int2* __restrict__ chunks,
+                                                   AdamGroups hp, AdamScalars s) {
+  const int2 ch = chunks[blockIdx.x];
+  const AdamTensor t = tensors[ch.x];
+  const float wd = hp.wd[t.group & 7], neg_step = -t.step_size, bc2_sqrt = t.bc2_sqrt;
+  const bool small_w = fabsf(s.w1) < 0.5f;
+  const int64_t base = (int64_t)ch.y * kEmaChunk;
+  // 16-byte accesses where the whole chunk lies inside the tensor and every pointer allows them (a gradient inside a
+  // flat reduction buffer may sit at any 4-byte offset); `base` is a multiple of 4096 elements, so alignment is the pointers'
+  const uintptr_t bits = (uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.g2 | (uintptr_t)t.m | (uintptr_t)t.v;
+  if ((bits & 15) == 0 && base + kEmaChunk <= t.n) {
+#pragma unroll 2
+    for (int j = 0; j < 4; ++j) {
+      const int64_t i = base + (j * 256 + threadIdx.x) * 4;
+      f32x4 p = *reinterpret_cast<const f32x4*>(t.p + i), g = *reinterpret_cast<const f32x4*>(t.g + i);
+      f32x4 m = *reinterpret_cast<const f32x4*>(t.m + i), v = *reinterpret_cast<const f32x4*>(t.v + i);
+      if (t.g2) {
+        const f32x4 g2 = *reinterpret_cast<const f32x4*>(t.g2 + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) g[e] = g2[e] + g[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = p[e], me = m[e], ve = v[e];
+        adam_element(pe, g[e], me, ve, wd, neg_step, bc2_sqrt, s, small_w);
+        p[e] = pe, m[e] = me, v[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(t.m + i) = m;
+      *reinterpret_cast<f32x4*>(t.v + i) = v;
+      *reinterpret_cast<f32x4*>(t.p + i) = p;
+    }
+    return;
+  }
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int64_t i = base + j * 256 + threadIdx.x;
+    if (i < t.n) {
+      float p = t.p[i], g = t.g[i], m = t.m[i], v = t.v[i];
+      if (t.g2) g = t.g2[i] + g;
+      adam_element(p, g, m, v, wd, neg_step, bc2_sqrt, s, small_w);
+      t.m[i] = m;
+      t.v[i] = v;
+      t.p[i] = p;
     }
   }
 }
@@ -555,18 +662,57 @@ extern "C" int dasac_ema_update(const void* pairs, int n_tensors, const int32_t*
   return DASAC_OK;
 }
 
-extern "C" int dasac_sgd_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_lr,
-                              const float* group_wd, int n_groups, float momentum, int first, dasac_stream_t stream) {
-  DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_step: bad arguments");
-  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_step: 1..8 parameter groups");
+static SgdGroups sgd_groups(const float* group_lr, const float* group_wd, int n_groups) {
   SgdGroups hp;
   for (int i = 0; i < 8; ++i) {
     hp.lr[i] = i < n_groups ? group_lr[i] : 0.f;
     hp.wd[i] = i < n_groups ? group_wd[i] : 0.f;
   }
-  hipLaunchKernelGGL(sgd_chunks, dim3(n_chunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const SgdTensor*>(tensors),
+  return hp;
+}
+
+template <bool NESTEROV>
+static int launch_sgd(const void* tensors, const int32_t* chunks, int n_chunks, const SgdGroups& hp, float momentum, int first,
+                      dasac_stream_t stream) {
+  hipLaunchKernelGGL(sgd_chunks<NESTEROV>, dim3(n_chunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const SgdTensor*>(tensors),
                      reinterpret_cast<const int2*>(chunks), hp, momentum, first);
   DASAC_CHECK_LAUNCH("sgd_chunks");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_sgd_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_lr,
+                              const float* group_wd, int n_groups, float momentum, int first, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_step: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_step: 1..8 parameter groups");
+  return launch_sgd<false>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, stream);
+}
+
+extern "C" int dasac_sgd_nesterov_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                                       const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
+                                       dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_nesterov_step: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_nesterov_step: 1..8 parameter groups");
+  DASAC_REQUIRE(momentum > 0.f, "sgd_nesterov_step: Nesterov momentum requires a momentum");
+  return launch_sgd<true>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, stream);
+}
+
+extern "C" int dasac_adam_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_wd,
+                               int n_groups, double beta1, double beta2, double eps, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_wd && n_tensors > 0 && n_chunks > 0, "adam_step: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "adam_step: 1..8 parameter groups");
+  DASAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adam_step: betas in [0, 1), eps >= 0");
+  AdamGroups hp;
+  for (int i = 0; i < 8; ++i) hp.wd[i] = i < n_groups ? group_wd[i] : 0.f;
+  // adam.py:706,720 form 1 - beta in python doubles; the foreach functors then round each scalar to fp32 once
+  AdamScalars s;
+  s.w1 = (float)(1.0 - beta1);
+  s.one_minus_w1 = 1.f - s.w1;                  // Lerp.h:34, opmath_t(1) - weight
+  s.beta2 = (float)beta2;
+  s.w2 = (float)(1.0 - beta2);
+  s.eps = (float)eps;
+  hipLaunchKernelGGL(adam_chunks, dim3(n_chunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const AdamTensor*>(tensors),
+                     reinterpret_cast<const int2*>(chunks), hp, s);
+  DASAC_CHECK_LAUNCH("adam_chunks");
   return DASAC_OK;
 }
 

@@ -53,6 +53,8 @@ PROTOTYPES = {
     "dasac_ema_chunk_elems": (_i, []),
     "dasac_ema_update": (_i, [_p, _i, _p, _i, _f, _i, _p, _p, _p]),
     "dasac_sgd_step": (_i, [_p, _i, _p, _i, _p, _p, _i, _f, _i, _p]),
+    "dasac_sgd_nesterov_step": (_i, [_p, _i, _p, _i, _p, _p, _i, _f, _i, _p]),
+    "dasac_adam_step": (_i, [_p, _i, _p, _i, _p, _i, C.c_double, C.c_double, C.c_double, _p]),
     "dasac_scale_planes": (_i, [_p, _p, _l, _l, _p, _p]),
     "dasac_add": (_i, [_p, _p, _p, _l, _p]),
     "dasac_relu_mask": (_i, [_p, _p, _p, _l, _p]),

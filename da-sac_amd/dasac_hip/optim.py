@@ -1,8 +1,9 @@
-"""Fused multi-tensor SGD for the reference's optimiser (base_trainer.py:63-66:
-`torch.optim.SGD(param_groups, momentum=MOMENTUM, nesterov=OPT_NESTEROV)` over the four groups of
-models/basenet.py:73-95).  Same update rule, `param_groups` and `state[p]["momentum_buffer"]` layout as
-torch.optim.SGD (so LR schedules that poke `param_groups[i]["lr"]` and optimiser checkpoints keep working), but one
-HIP launch (dasac_sgd_step) instead of ~4 foreach passes per group."""
+"""Fused multi-tensor optimisers for the three cases of the reference's factory (base_trainer.py:47-73):
+`torch.optim.SGD(param_groups, momentum=MOMENTUM, nesterov=OPT_NESTEROV)` (:63-66) and
+`torch.optim.Adam(param_groups, betas=(BETA1, 0.999))` (:57-61) over the four groups of models/basenet.py:73-95.
+Same update rules, `param_groups` and `state[p]` layouts as the torch classes (so LR schedules that poke
+`param_groups[i]["lr"]` and optimiser checkpoints keep working, in both directions), but one HIP launch per step
+(dasac_sgd_step / dasac_sgd_nesterov_step / dasac_adam_step) instead of a chain of foreach passes per group."""
 import ctypes
 
 import numpy as np
@@ -12,15 +13,16 @@ from . import lib as L
 from . import ops
 
 
-class FusedSGD(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, dampening=0.0):
-        if nesterov or dampening != 0.0:
-            raise NotImplementedError("FusedSGD: plain momentum only (the reference's default OPT_NESTEROV=False)")
-        defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False)
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What the fused optimisers share: the stash of an earlier backward pass' gradients, the walk over the parameters
+    that have something to apply, and the upload of the per-step pointer table."""
+    MAX_GROUPS = 8
+
+    def __init__(self, params, defaults):
         super().__init__(params, defaults)
-        if len(self.param_groups) > 8:
-            raise ValueError("FusedSGD: at most 8 parameter groups")
-        self._tables = {}            # first(bool) -> (pointer key, device tensor table, device chunk table, n_tensors, n_chunks)
+        if len(self.param_groups) > self.MAX_GROUPS:
+            raise ValueError("{}: at most {} parameter groups".format(type(self).__name__, self.MAX_GROUPS))
+        self._tables = {}            # slot -> (key, device tensor table, device chunk table, n_tensors, n_chunks)
         self._stash = {}             # parameter -> gradient of an earlier backward pass, summed inside the next step()
 
     def stash_grads(self):
@@ -52,34 +54,11 @@ class FusedSGD(torch.optim.Optimizer):
         self._stash.clear()
         super().zero_grad(set_to_none=set_to_none)
 
-    def _table(self, first, rows, device):
-        key = tuple(v for r in rows for v in r)
-        ent = self._tables.get(first)
-        if ent is None or ent[0] != key:
-            chunk = L.load().dasac_ema_chunk_elems()
-            chunks = [(i, j) for i, r in enumerate(rows) for j in range((r[4] + chunk - 1) // chunk)]
-            # The gradients are fresh allocations every step, so this table is rebuilt every step: upload it through pinned
-            # memory without blocking.  A pageable source makes `.to(device)` wait for the WHOLE stream -- the backward pass
-            # still running on the device -- and the device then idles while the host catches up (measured: ~3 ms per step).
-            up = lambda a: torch.from_numpy(a).pin_memory().to(device, non_blocking=True)
-            ent = (key, up(np.asarray(rows, dtype=np.int64)), up(np.asarray(chunks, dtype=np.int32).reshape(-1, 2)),
-                   len(rows), len(chunks))
-            self._tables[first] = ent
-        return ent
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = L.load()
-        momentum = self.param_groups[0]["momentum"]
-        rows = {True: [], False: []}
-        device, keep, touched = None, [], []
+    def _pending(self):
+        """(group index, parameter, gradient, stashed gradient or None) of every parameter the next step() updates, checked
+        and made contiguous.  Nothing has been launched when this raises."""
+        name = type(self).__name__
         for gi, group in enumerate(self.param_groups):
-            if group["momentum"] != momentum or group.get("nesterov") or group.get("dampening", 0.0) != 0.0 or group.get("maximize"):
-                raise NotImplementedError("FusedSGD: one momentum for all groups, no nesterov / dampening / maximize")
             for p in group["params"]:
                 g2 = self._stash.get(p)
                 if p.grad is None:
@@ -88,29 +67,146 @@ class FusedSGD(torch.optim.Optimizer):
                     p.grad, g2 = g2, None            # only the stashed pass produced a gradient for this parameter
                 L.require_gpu(p, p.grad, g2)
                 if p.dtype != torch.float32 or not p.is_contiguous() or p.grad.is_sparse:
-                    raise TypeError("FusedSGD: dense contiguous fp32 parameters only")
+                    raise TypeError(name + ": dense contiguous fp32 parameters only")
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 if g2 is not None and not g2.is_contiguous():
                     g2 = g2.contiguous()
-                st = self.state[p]
-                first = st.get("momentum_buffer") is None
-                if first:
-                    st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
-                device = p.device
-                rows[first or momentum == 0.0].append((p.data_ptr(), g.data_ptr(), 0 if g2 is None else g2.data_ptr(),
-                                                       st["momentum_buffer"].data_ptr(), p.numel(), gi))
-                keep += [g, g2]                          # a made-contiguous copy must outlive the queued launch
-                touched += [p, st["momentum_buffer"]]
+                yield gi, p, g, g2
+
+    def _table(self, slot, key, rows, sizes, device):
+        """rows: int64 [n_tensors, k] host array; sizes: element counts -> the (tensor, chunk) list of the multi-tensor kernels."""
+        ent = self._tables.get(slot)
+        if ent is None or ent[0] != key:
+            chunk = L.load().dasac_ema_chunk_elems()
+            chunks = [(i, j) for i, n in enumerate(sizes) for j in range((n + chunk - 1) // chunk)]
+            # The gradients are fresh allocations every step, so this table is rebuilt every step: upload it through pinned
+            # memory without blocking.  A pageable source makes `.to(device)` wait for the WHOLE stream -- the backward pass
+            # still running on the device -- and the device then idles while the host catches up (measured: ~3 ms per step).
+            up = lambda a: torch.from_numpy(a).pin_memory().to(device, non_blocking=True)
+            ent = (key, up(rows), up(np.asarray(chunks, dtype=np.int32).reshape(-1, 2)), len(sizes), len(chunks))
+            self._tables[slot] = ent
+        return ent
+
+    def _group_floats(self, name):
+        return (ctypes.c_float * len(self.param_groups))(*[float(g[name]) for g in self.param_groups])
+
+
+class FusedSGD(_FusedOptimizer):
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, dampening=0.0):
+        if dampening != 0.0:
+            raise NotImplementedError("FusedSGD: no dampening (the reference never sets it)")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=bool(nesterov))
+        super().__init__(params, defaults)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = L.load()
+        momentum, nesterov = self.param_groups[0]["momentum"], bool(self.param_groups[0].get("nesterov"))
+        for group in self.param_groups:
+            if group["momentum"] != momentum or bool(group.get("nesterov")) != nesterov or group.get("dampening", 0.0) != 0.0 \
+                    or group.get("maximize"):
+                raise NotImplementedError("FusedSGD: one momentum and one nesterov setting for all groups, no dampening / maximize")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        rows = {True: [], False: []}
+        device, keep, touched = None, [], []
+        for gi, p, g, g2 in list(self._pending()):      # every check first: a refusal leaves no half-initialised state
+            st = self.state[p]
+            first = st.get("momentum_buffer") is None
+            if first:
+                st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+            device = p.device
+            rows[first or momentum == 0.0].append((p.data_ptr(), g.data_ptr(), 0 if g2 is None else g2.data_ptr(),
+                                                   st["momentum_buffer"].data_ptr(), p.numel(), gi))
+            keep += [g, g2]                          # a made-contiguous copy must outlive the queued launch
+            touched += [p, st["momentum_buffer"]]
         n = len(self.param_groups)
-        lr = (ctypes.c_float * n)(*[float(g["lr"]) for g in self.param_groups])
-        wd = (ctypes.c_float * n)(*[float(g["weight_decay"]) for g in self.param_groups])
+        lr, wd = self._group_floats("lr"), self._group_floats("weight_decay")
+        entry, what = (lib.dasac_sgd_nesterov_step, "dasac_sgd_nesterov_step") if nesterov else (lib.dasac_sgd_step, "dasac_sgd_step")
         for first in (True, False):
             if not rows[first]:
                 continue
-            _, tab, chunks, nt, nc = self._table(first, rows[first], device)
-            L.check(lib.dasac_sgd_step(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(lr, ctypes.c_void_p),
-                                       ctypes.cast(wd, ctypes.c_void_p), n, float(momentum), int(first), L.stream_ptr()),
-                    "dasac_sgd_step")
+            key = tuple(v for r in rows[first] for v in r)
+            _, tab, chunks, nt, nc = self._table(first, key, np.asarray(rows[first], dtype=np.int64), [r[4] for r in rows[first]], device)
+            L.check(entry(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(lr, ctypes.c_void_p),
+                          ctypes.cast(wd, ctypes.c_void_p), n, float(momentum), int(first), L.stream_ptr()), what)
         ops.bump_versions(touched)       # raw-pointer writes: keep autograd's version counters (engine cache keys) honest
+        self._stash.clear()
+        return loss
+
+
+class FusedAdam(_FusedOptimizer):
+    """torch.optim.Adam as the reference builds it: L2 weight decay added to the gradient, no amsgrad.  `state[p]` holds
+    `step` (a host fp32 tensor, as torch keeps it), `exp_avg` and `exp_avg_sq`; the group keys are torch.optim.Adam's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
+                 capturable=False):
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay:
+            raise ValueError("FusedAdam: lr, eps and weight_decay must not be negative")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError("FusedAdam: betas must lie in [0, 1)")
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None,
+                        capturable=capturable, differentiable=False, fused=None, decoupled_weight_decay=False)
+        super().__init__(params, defaults)
+        self._hyper()
+
+    def _hyper(self):
+        """(beta1, beta2, eps) of the one launch; refuses what the kernel does not do."""
+        g0 = self.param_groups[0]
+        for group in self.param_groups:
+            if any(group.get(k) for k in ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")):
+                raise NotImplementedError("FusedAdam: no amsgrad / maximize / capturable / differentiable / decoupled weight decay")
+            if tuple(group["betas"]) != tuple(g0["betas"]) or group["eps"] != g0["eps"]:
+                raise NotImplementedError("FusedAdam: one betas / eps for all groups")
+        return float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = L.load()
+        beta1, beta2, eps = self._hyper()
+        ptrs, scalars, device, keep, touched, steps = [], [], None, [], [], []
+        for gi, p, g, g2 in list(self._pending()):      # every check first: a refusal leaves no half-initialised state
+            st = self.state[p]
+            if len(st) == 0:                          # torch/optim/adam.py, _init_group
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            L.require_gpu(m, v)
+            if m.dtype != torch.float32 or v.dtype != torch.float32 or not m.is_contiguous() or not v.is_contiguous():
+                raise TypeError("FusedAdam: dense contiguous fp32 state only")
+            device = p.device
+            ptrs.append((p.data_ptr(), g.data_ptr(), 0 if g2 is None else g2.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), gi))
+            steps.append((st, float(self.param_groups[gi]["lr"])))
+            keep += [g, g2]                          # a made-contiguous copy must outlive the queued launch
+            touched += [p, m, v]
+        if ptrs:
+            for st, lr in steps:                     # only now: a refusal above leaves every step count as it was
+                if not torch.is_tensor(st["step"]):       # a checkpoint from before torch kept `step` as a tensor
+                    st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+                st["step"] += 1
+                step = st["step"].item()
+                # the python doubles of adam.py:772-781; each tensor has its own step count (a parameter whose first gradient
+                # arrives later takes larger bias corrections than its neighbours)
+                scalars.append((lr / (1 - beta1 ** step), (1 - beta2 ** step) ** 0.5))
+            rows = np.zeros((len(ptrs), 8), dtype=np.int64)
+            rows[:, :7] = np.asarray(ptrs, dtype=np.int64)
+            rows.view(np.float32)[:, 14:16] = np.asarray(scalars, dtype=np.float64)         # rounded to fp32 here, once
+            key = tuple(v for r in ptrs for v in r) + tuple(v for r in scalars for v in r)
+            _, tab, chunks, nt, nc = self._table(0, key, rows, [r[5] for r in ptrs], device)
+            wd = self._group_floats("weight_decay")
+            L.check(lib.dasac_adam_step(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(wd, ctypes.c_void_p),
+                                        len(self.param_groups), beta1, beta2, eps, L.stream_ptr()), "dasac_adam_step")
+            ops.bump_versions(touched)   # raw-pointer writes: keep autograd's version counters (engine cache keys) honest
         self._stash.clear()
         return loss

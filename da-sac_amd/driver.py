@@ -8,9 +8,11 @@ import torch
 def make_optimizer(net, cfg_model, fused=True):
     """`BaseTrainer.get_optim` (base_trainer.py:47-73) over the model's four parameter groups (train.py:93-96):
       OPT == "SGD" (the default, configs/*.yaml): SGD(momentum, nesterov=OPT_NESTEROV) -- the fused multi-tensor HIP optimiser
-          (same update rule / state layout; plain momentum only) or, with fused=False / nesterov, torch.optim.SGD itself;
+          (same update rule / state layout) for plain momentum or, with fused=False / nesterov, torch.optim.SGD itself;
       OPT == "Adam": torch.optim.Adam(lr, betas=(BETA1, 0.999), weight_decay) (base_trainer.py:57-61);
       any other name in torch.optim: optim(params, lr=LR) (base_trainer.py:68-69); unknown names raise NotImplementedError.
+    fused="all" also returns the HIP optimisers for the other two cases of the factory: `FusedSGD(nesterov=True)` under
+    OPT_NESTEROV and `FusedAdam` under OPT == "Adam" (anything else as under fused=True).
     Every group carries its own lr / weight_decay (basenet.py:102-139), so the keyword defaults below only fill the gaps,
     exactly as in the reference."""
     core = net.module if hasattr(net, "module") else net
@@ -19,13 +21,19 @@ def make_optimizer(net, cfg_model, fused=True):
     if not hasattr(torch.optim, opt):
         print("Optimiser {} not supported".format(opt))
         raise NotImplementedError
+    fuse_all = isinstance(fused, str) and fused == "all"
     if opt == "Adam":
-        upd = torch.optim.Adam(groups, lr=cfg_model.LR, betas=(getattr(cfg_model, "BETA1", 0.5), 0.999), weight_decay=cfg_model.WEIGHT_DECAY)
+        betas = (getattr(cfg_model, "BETA1", 0.5), 0.999)
+        if fuse_all:
+            from dasac_hip.optim import FusedAdam
+            upd = FusedAdam(groups, lr=cfg_model.LR, betas=betas, weight_decay=cfg_model.WEIGHT_DECAY)
+        else:
+            upd = torch.optim.Adam(groups, lr=cfg_model.LR, betas=betas, weight_decay=cfg_model.WEIGHT_DECAY)
     elif opt == "SGD":
         nesterov = getattr(cfg_model, "OPT_NESTEROV", False)
-        if fused and not nesterov:
+        if fused and (fuse_all or not nesterov):
             from dasac_hip.optim import FusedSGD
-            upd = FusedSGD(groups, lr=cfg_model.LR, momentum=cfg_model.MOMENTUM, weight_decay=cfg_model.WEIGHT_DECAY)
+            upd = FusedSGD(groups, lr=cfg_model.LR, momentum=cfg_model.MOMENTUM, weight_decay=cfg_model.WEIGHT_DECAY, nesterov=nesterov)
         else:
             upd = torch.optim.SGD(groups, lr=cfg_model.LR, momentum=cfg_model.MOMENTUM, nesterov=nesterov, weight_decay=cfg_model.WEIGHT_DECAY)
     else:
@@ -127,12 +135,14 @@ def sac_train_iteration(net, optim, src_batch, tgt_batch, group_size, update_tea
     (train.py:274-276) and clears the gradients before the target backward (train.py:226-227).
 
     The reference lets autograd add the target-pass gradients onto the source-pass ones in `.grad` (320 `add_` launches for
-    ResNet-101).  With `FusedSGD` the source gradients are set aside instead (`stash_grads`) and the update kernel applies
+    ResNet-101).  With a fused optimiser (`FusedSGD`, plain or Nesterov, and `FusedAdam`: anything that has `stash_grads`) the
+    source gradients are set aside instead and the update kernel applies
     source + target -- on one rank the same sum, bit for bit.  Between the target backward and step(), and after it,
     `.grad` holds the target-pass gradient only: anything that reads gradients before the step (clipping, norm logging)
     must use `optim.full_grads()` or pass sum_grads_in_optimizer=False (or another optimiser) for the reference's `.grad`
     contents.  Under data parallelism the update is mean_r(src_r) + mean_r(tgt_r) where the reference's DDP reduces
-    mean_r(mean(src) + tgt_r): equal in exact arithmetic, one rounding apart in fp32 (not bit-identical).
+    mean_r(mean(src) + tgt_r): equal in exact arithmetic, one rounding apart in fp32 (not bit-identical) -- for every fused
+    optimiser alike.
 
     fuse_passes=True: the student runs ONCE over [source crops; target crops] and ONE backward pass differentiates
     loss_ce + LR_TARGET * self_ce (`SAC.forward_fused`: same weights in both passes, frozen BN, teacher independent of the

@@ -296,6 +296,24 @@ int dasac_ema_chunk_elems(void);
 int dasac_sgd_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
                    const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
                    dasac_stream_t stream);
+/* The same with Nesterov momentum (OPT_NESTEROV, base_trainer.py:64; torch/optim/sgd.py:462-473): buf as above, then
+ * p -= lr*(d + momentum*buf).  Table, chunks, group arrays and the `first` split are those of dasac_sgd_step; momentum > 0. */
+int dasac_sgd_nesterov_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                            const float* group_lr, const float* group_wd, int n_groups, float momentum,
+                            int first, dasac_stream_t stream);
+/* torch.optim.Adam (OPT: Adam, base_trainer.py:57-61 with betas = (BETA1, 0.999), core/config.py:135-140: BETA1 = 0.5) over all
+ * parameters of up to 8 groups in ONE launch: L2 weight decay in the gradient, no amsgrad, no maximize, not decoupled.  Per
+ * element, in the operation order of torch/optim/adam.py:689-800 (foreach, not capturable):
+ *   g = (g2 +) g (+ wd*p);  m = lerp(m, g, 1 - beta1) (ATen's two-branch lerp, Lerp.h:32-34);  v = v*beta2 + (1 - beta2)*(g*g);
+ *   p += -step_size * (m / (sqrt(v)/bc2_sqrt + eps)).
+ * tensors: device array of 64-byte rows {float* p; const float* g; const float* g2 (NULL or a second gradient, as for
+ * dasac_sgd_step); float* exp_avg; float* exp_avg_sq; int64 n; int32 group; int32 reserved; float step_size; float bc2_sqrt}
+ * with step_size = lr/(1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) of THAT tensor's step count, computed by the caller
+ * in doubles as adam.py:772-781 does and rounded to fp32.  chunks as for dasac_ema_update; group_wd: HOST array.  1 - beta1
+ * and 1 - beta2 are formed in double here and rounded to fp32 once, as the foreach kernels receive them. */
+int dasac_adam_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                    const float* group_wd, int n_groups, double beta1, double beta2, double eps,
+                    dasac_stream_t stream);
 int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks,
                      float momentum, int update, double* sq, float* out, dasac_stream_t stream);
 int dasac_scale_planes(const float* x, const float* plane_scale, int64_t planes, int64_t HW,
