@@ -425,13 +425,50 @@ __device__ __forceinline__ float mul_add(float a, float b, float c) {
   return FMA ? __fmaf_rn(a, b, c) : a * b + c;
 }
 
-template <bool NESTEROV>
+// ---- global gradient-norm clipping / non-finite step skipping: the device control block -----------------
+// Written by grad_norm_finish (below the update kernels), read by the CTL forms of sgd_chunks / adam_chunks.  The update
+// needs ONE global fact before any parameter may be written -- the L2 norm of g2 + g over ALL parameters -- and takes it from
+// here, so the host never sees it (no synchronisation).  flags: kCtlClip multiplies the summed gradient by `coef` (one fp32
+// multiply, before weight decay: what clip_grad_norm_ does to .grad); kCtlSkip makes every block return without a write while
+// `skip` is set.
+struct GradCtl {
+  float total;          // ||g2 + g||_2 over every tensor of the table, before clipping
+  float coef;           // min(max_norm / (total + 1e-6), 1), NaN kept as torch.clamp keeps it; 1 when only measuring
+  int32_t skip;         // total is not finite
+  int32_t reserved;
+};
+static_assert(sizeof(GradCtl) == 16, "GradCtl is the 16-byte control block of include/dasac_hip.h");
+constexpr int kCtlClip = 1, kCtlSkip = 2;
+
+// CTL = false is the kernel as it has always been (`ctl` / `flags` unused).  CTL = true: `first` may be -1, then bit 32 of each
+// row's `group` says whether THAT tensor takes its first step -- one table and one norm for the whole step.  A skipped first step
+// still writes buf = -0: the host has allocated the buffer and will call the next step a later one, whose momentum*(-0) + d is
+// d for every d (a +0 would turn d = -0 into +0), i.e. exactly the first-step rule.
+template <bool NESTEROV, bool CTL>
 __global__ __launch_bounds__(256) void sgd_chunks(const SgdTensor* __restrict__ tensors, const int2* __restrict__ chunks,
-                                                  SgdGroups hp, float momentum, int first) {
+                                                  SgdGroups hp, float momentum, int first, const GradCtl* __restrict__ ctl, int flags) {
   const int2 ch = chunks[blockIdx.x];
   const SgdTensor t = tensors[ch.x];
-  const float lr = hp.lr[t.group], wd = hp.wd[t.group];
+  const int64_t group = CTL ? (t.group & 7) : t.group;
+  const float lr = hp.lr[group], wd = hp.wd[group];
   const int64_t base = (int64_t)ch.y * kEmaChunk;
+  bool clip = false;
+  float coef = 1.f;
+  if (CTL) {
+    if (first < 0) first = (int)((t.group >> 32) & 1);
+    if ((flags & kCtlSkip) && ctl->skip) {
+      if (first) {
+#pragma unroll 4
+        for (int j = 0; j < 16; ++j) {
+          const int64_t i = base + j * 256 + threadIdx.x;
+          if (i < t.n) t.buf[i] = -0.f;
+        }
+      }
+      return;
+    }
+    clip = (flags & kCtlClip) != 0;
+    coef = ctl->coef;
+  }
 #pragma unroll 4
   for (int j = 0; j < 16; ++j) {
     const int64_t i = base + j * 256 + threadIdx.x;
@@ -439,6 +476,9 @@ __global__ __launch_bounds__(256) void sgd_chunks(const SgdTensor* __restrict__ 
       const float p = t.p[i];
       float d = t.g[i];
       if (t.g2) d = t.g2[i] + d;
+      if (CTL) {
+        if (clip) d = d * coef;
+      }
       if (wd != 0.f) d = mul_add<NESTEROV>(wd, p, d);
       float b = d;
       if (!first) {
@@ -500,13 +540,22 @@ __device__ __forceinline__ void adam_element(float& p, float g, float& m, float&
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));      // 16-byte aligned: one global_load/store_dwordx4
+// CTL = false is the kernel as it has always been (`ctl` / `flags` unused); CTL = true: GradCtl above.
+template <bool CTL>
 __global__ __launch_bounds__(256) void adam_chunks(const AdamTensor* __restrict__ tensors, const int2* __restrict__ chunks,
-                                                   AdamGroups hp, AdamScalars s) {
+                                                   AdamGroups hp, AdamScalars s, const GradCtl* __restrict__ ctl, int flags) {
   const int2 ch = chunks[blockIdx.x];
   const AdamTensor t = tensors[ch.x];
   const float wd = hp.wd[t.group & 7], neg_step = -t.step_size, bc2_sqrt = t.bc2_sqrt;
   const bool small_w = fabsf(s.w1) < 0.5f;
   const int64_t base = (int64_t)ch.y * kEmaChunk;
+  bool clip = false;
+  float coef = 1.f;
+  if (CTL) {
+    if ((flags & kCtlSkip) && ctl->skip) return;      // p, m and v stay as they are
+    clip = (flags & kCtlClip) != 0;
+    coef = ctl->coef;
+  }
   // 16-byte accesses where the whole chunk lies inside the tensor and every pointer allows them (a gradient inside a
   // flat reduction buffer may sit at any 4-byte offset); `base` is a multiple of 4096 elements, so alignment is the pointers'
   const uintptr_t bits = (uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.g2 | (uintptr_t)t.m | (uintptr_t)t.v;
@@ -520,6 +569,12 @@ __global__ __launch_bounds__(256) void adam_chunks(const AdamTensor* __restrict_
         const f32x4 g2 = *reinterpret_cast<const f32x4*>(t.g2 + i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) g[e] = g2[e] + g[e];
+      }
+      if (CTL) {
+        if (clip) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) g[e] = g[e] * coef;
+        }
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -539,11 +594,90 @@ __global__ __launch_bounds__(256) void adam_chunks(const AdamTensor* __restrict_
     if (i < t.n) {
       float p = t.p[i], g = t.g[i], m = t.m[i], v = t.v[i];
       if (t.g2) g = t.g2[i] + g;
+      if (CTL) {
+        if (clip) g = g * coef;
+      }
       adam_element(p, g, m, v, wd, neg_step, bc2_sqrt, s, small_w);
       t.m[i] = m;
       t.v[i] = v;
       t.p[i] = p;
     }
+  }
+}
+
+// ---- ||g2 + g||_2 over every tensor of an optimiser table, and the control block the CTL update kernels read ---------
+// One double partial per (tensor, chunk) of the update kernels' own tables (rows of `row_bytes`: g at byte 8, g2 at 16, n at
+// `n_off`), no atomics; grad_norm_finish adds the partials in a fixed order: the same inputs give the same bits.  d = g2 + g is
+// the fp32 sum the update applies (AccumulateGrad's operand order); d*d is exact in double.  Thread t owns elements
+// (j*256 + t)*4 + e of the chunk on BOTH paths -- one dwordx4 load per j where the chunk is whole and both pointers are
+// 16-byte aligned, four guarded scalar loads otherwise -- and adds them in the same order, so the norm does not depend on
+// where a gradient happens to lie (a view into a flat reduction buffer may sit at any 4-byte offset).
+__global__ __launch_bounds__(256) void grad_sq_chunks(const char* __restrict__ rows, int row_bytes, int n_off,
+                                                      const int2* __restrict__ chunks, double* __restrict__ sq_chunk) {
+  const int2 ch = chunks[blockIdx.x];
+  const char* row = rows + (size_t)ch.x * row_bytes;
+  const float* g = *reinterpret_cast<const float* const*>(row + 8);
+  const float* g2 = *reinterpret_cast<const float* const*>(row + 16);
+  const int64_t n = *reinterpret_cast<const int64_t*>(row + n_off);
+  const int64_t base = (int64_t)ch.y * kEmaChunk;
+  double acc = 0;
+  if ((((uintptr_t)g | (uintptr_t)g2) & 15) == 0 && base + kEmaChunk <= n) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t i = base + (j * 256 + threadIdx.x) * 4;
+      f32x4 d = *reinterpret_cast<const f32x4*>(g + i);
+      if (g2) {
+        const f32x4 d2 = *reinterpret_cast<const f32x4*>(g2 + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = d2[e] + d[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc += (double)d[e] * (double)d[e];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int64_t i = base + (j * 256 + threadIdx.x) * 4 + e;
+        if (i < n) {
+          float d = g[i];
+          if (g2) d = g2[i] + d;
+          acc += (double)d * (double)d;
+        }
+      }
+    }
+  }
+  __shared__ double red[4];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) sq_chunk[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);      // one partial per chunk: no atomics
+}
+
+// total, coef and the skip flag from the chunk partials; in fp32 from the square root on, as torch.nn.utils.clip_grad_norm_
+// computes them.  A NaN norm gives a NaN coef (torch.clamp keeps NaN; fminf would not).  One block, fixed summation order.
+__global__ __launch_bounds__(256) void grad_norm_finish(const double* __restrict__ sq_chunk, int n_chunks, float max_norm,
+                                                        GradCtl* __restrict__ ctl, int64_t* __restrict__ skipped) {
+  double s = 0;
+  for (int i = threadIdx.x; i < n_chunks; i += 256) s += sq_chunk[i];
+  __shared__ double red[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float total = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+      const float c = max_norm / (total + 1e-6f);
+      coef = c > 1.f ? 1.f : c;
+    }
+    const int skip = isfinite(total) ? 0 : 1;
+    ctl->total = total;
+    ctl->coef = coef;
+    ctl->skip = skip;
+    ctl->reserved = 0;
+    if (skipped) *skipped += skip;
   }
 }
 
@@ -671,11 +805,12 @@ static SgdGroups sgd_groups(const float* group_lr, const float* group_wd, int n_
   return hp;
 }
 
-template <bool NESTEROV>
+template <bool NESTEROV, bool CTL>
 static int launch_sgd(const void* tensors, const int32_t* chunks, int n_chunks, const SgdGroups& hp, float momentum, int first,
-                      dasac_stream_t stream) {
-  hipLaunchKernelGGL(sgd_chunks<NESTEROV>, dim3(n_chunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const SgdTensor*>(tensors),
-                     reinterpret_cast<const int2*>(chunks), hp, momentum, first);
+                      const void* ctl, int flags, dasac_stream_t stream) {
+  hipLaunchKernelGGL((sgd_chunks<NESTEROV, CTL>), dim3(n_chunks), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const SgdTensor*>(tensors), reinterpret_cast<const int2*>(chunks), hp, momentum, first,
+                     reinterpret_cast<const GradCtl*>(ctl), flags);
   DASAC_CHECK_LAUNCH("sgd_chunks");
   return DASAC_OK;
 }
@@ -684,7 +819,7 @@ extern "C" int dasac_sgd_step(const void* tensors, int n_tensors, const int32_t*
                               const float* group_wd, int n_groups, float momentum, int first, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_step: bad arguments");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_step: 1..8 parameter groups");
-  return launch_sgd<false>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, stream);
+  return launch_sgd<false, false>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, nullptr, 0, stream);
 }
 
 extern "C" int dasac_sgd_nesterov_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
@@ -693,14 +828,39 @@ extern "C" int dasac_sgd_nesterov_step(const void* tensors, int n_tensors, const
   DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_nesterov_step: bad arguments");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_nesterov_step: 1..8 parameter groups");
   DASAC_REQUIRE(momentum > 0.f, "sgd_nesterov_step: Nesterov momentum requires a momentum");
-  return launch_sgd<true>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, stream);
+  return launch_sgd<true, false>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, nullptr, 0, stream);
 }
 
-extern "C" int dasac_adam_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_wd,
-                               int n_groups, double beta1, double beta2, double eps, dasac_stream_t stream) {
-  DASAC_REQUIRE(tensors && chunks && group_wd && n_tensors > 0 && n_chunks > 0, "adam_step: bad arguments");
-  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "adam_step: 1..8 parameter groups");
-  DASAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adam_step: betas in [0, 1), eps >= 0");
+static bool ctl_args_ok(const void* ctl, int apply_coef, int honour_skip) {
+  return ctl && ((uintptr_t)ctl & 15) == 0 && (apply_coef == 0 || apply_coef == 1) && (honour_skip == 0 || honour_skip == 1);
+}
+
+extern "C" int dasac_sgd_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_lr,
+                                  const float* group_wd, int n_groups, float momentum, int first, const void* ctl, int apply_coef,
+                                  int honour_skip, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_step_ctl: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_step_ctl: 1..8 parameter groups");
+  DASAC_REQUIRE(first >= -1 && first <= 1, "sgd_step_ctl: first is 0, 1 or -1 (per row)");
+  DASAC_REQUIRE(ctl_args_ok(ctl, apply_coef, honour_skip), "sgd_step_ctl: a 16-byte aligned control block and 0/1 flags");
+  return launch_sgd<false, true>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, ctl,
+                                 apply_coef * kCtlClip + honour_skip * kCtlSkip, stream);
+}
+
+extern "C" int dasac_sgd_nesterov_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                                           const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
+                                           const void* ctl, int apply_coef, int honour_skip, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_nesterov_step_ctl: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_nesterov_step_ctl: 1..8 parameter groups");
+  DASAC_REQUIRE(momentum > 0.f, "sgd_nesterov_step_ctl: Nesterov momentum requires a momentum");
+  DASAC_REQUIRE(first >= -1 && first <= 1, "sgd_nesterov_step_ctl: first is 0, 1 or -1 (per row)");
+  DASAC_REQUIRE(ctl_args_ok(ctl, apply_coef, honour_skip), "sgd_nesterov_step_ctl: a 16-byte aligned control block and 0/1 flags");
+  return launch_sgd<true, true>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, ctl,
+                                apply_coef * kCtlClip + honour_skip * kCtlSkip, stream);
+}
+
+template <bool CTL>
+static int launch_adam(const void* tensors, const int32_t* chunks, int n_chunks, const float* group_wd, int n_groups, double beta1,
+                       double beta2, double eps, const void* ctl, int flags, dasac_stream_t stream) {
   AdamGroups hp;
   for (int i = 0; i < 8; ++i) hp.wd[i] = i < n_groups ? group_wd[i] : 0.f;
   // adam.py:706,720 form 1 - beta in python doubles; the foreach functors then round each scalar to fp32 once
@@ -710,9 +870,51 @@ extern "C" int dasac_adam_step(const void* tensors, int n_tensors, const int32_t
   s.beta2 = (float)beta2;
   s.w2 = (float)(1.0 - beta2);
   s.eps = (float)eps;
-  hipLaunchKernelGGL(adam_chunks, dim3(n_chunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const AdamTensor*>(tensors),
-                     reinterpret_cast<const int2*>(chunks), hp, s);
+  hipLaunchKernelGGL(adam_chunks<CTL>, dim3(n_chunks), dim3(256), 0, as_stream(stream), reinterpret_cast<const AdamTensor*>(tensors),
+                     reinterpret_cast<const int2*>(chunks), hp, s, reinterpret_cast<const GradCtl*>(ctl), flags);
   DASAC_CHECK_LAUNCH("adam_chunks");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_adam_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_wd,
+                               int n_groups, double beta1, double beta2, double eps, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_wd && n_tensors > 0 && n_chunks > 0, "adam_step: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "adam_step: 1..8 parameter groups");
+  DASAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adam_step: betas in [0, 1), eps >= 0");
+  return launch_adam<false>(tensors, chunks, n_chunks, group_wd, n_groups, beta1, beta2, eps, nullptr, 0, stream);
+}
+
+extern "C" int dasac_adam_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_wd,
+                                   int n_groups, double beta1, double beta2, double eps, const void* ctl, int apply_coef,
+                                   int honour_skip, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && group_wd && n_tensors > 0 && n_chunks > 0, "adam_step_ctl: bad arguments");
+  DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "adam_step_ctl: 1..8 parameter groups");
+  DASAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adam_step_ctl: betas in [0, 1), eps >= 0");
+  DASAC_REQUIRE(ctl_args_ok(ctl, apply_coef, honour_skip), "adam_step_ctl: a 16-byte aligned control block and 0/1 flags");
+  return launch_adam<true>(tensors, chunks, n_chunks, group_wd, n_groups, beta1, beta2, eps, ctl,
+                           apply_coef * kCtlClip + honour_skip * kCtlSkip, stream);
+}
+
+extern "C" size_t dasac_grad_norm_workspace(int n_chunks) { return n_chunks > 0 ? (size_t)n_chunks * sizeof(double) : 0; }
+
+extern "C" int dasac_grad_norm(const void* tensors, int row_bytes, int n_tensors, const int32_t* chunks, int n_chunks, float max_norm,
+                               void* workspace, size_t workspace_bytes, void* ctl, int64_t* skipped, dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && workspace && ctl && n_tensors > 0 && n_chunks > 0, "grad_norm: bad arguments");
+  DASAC_REQUIRE(row_bytes == (int)sizeof(SgdTensor) || row_bytes == (int)sizeof(AdamTensor),
+                "grad_norm: row_bytes names the table, 48 (dasac_sgd_step) or 64 (dasac_adam_step)");
+  DASAC_REQUIRE(workspace_bytes >= dasac_grad_norm_workspace(n_chunks) && ((uintptr_t)workspace & 7) == 0, "grad_norm: workspace too small");
+  DASAC_REQUIRE(((uintptr_t)ctl & 15) == 0 && ((uintptr_t)skipped & 7) == 0, "grad_norm: misaligned control block / counter");
+  DASAC_REQUIRE(max_norm == max_norm && max_norm <= 3.4028234664e38f, "grad_norm: max_norm is a finite number (<= 0: measure only)");
+  hipStream_t s = as_stream(stream);
+  const int n_off = row_bytes == (int)sizeof(SgdTensor) ? (int)offsetof(SgdTensor, n) : (int)offsetof(AdamTensor, n);
+  static_assert(offsetof(SgdTensor, g) == 8 && offsetof(SgdTensor, g2) == 16 && offsetof(AdamTensor, g) == 8 && offsetof(AdamTensor, g2) == 16,
+                "grad_sq_chunks reads g and g2 at bytes 8 and 16 of either row");
+  double* sq_chunk = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(grad_sq_chunks, dim3(n_chunks), dim3(256), 0, s, reinterpret_cast<const char*>(tensors), row_bytes, n_off,
+                     reinterpret_cast<const int2*>(chunks), sq_chunk);
+  DASAC_CHECK_LAUNCH("grad_sq_chunks");
+  hipLaunchKernelGGL(grad_norm_finish, dim3(1), dim3(256), 0, s, sq_chunk, n_chunks, max_norm, reinterpret_cast<GradCtl*>(ctl), skipped);
+  DASAC_CHECK_LAUNCH("grad_norm_finish");
   return DASAC_OK;
 }
 

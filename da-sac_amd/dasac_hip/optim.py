@@ -3,8 +3,15 @@
 `torch.optim.Adam(param_groups, betas=(BETA1, 0.999))` (:57-61) over the four groups of models/basenet.py:73-95.
 Same update rules, `param_groups` and `state[p]` layouts as the torch classes (so LR schedules that poke
 `param_groups[i]["lr"]` and optimiser checkpoints keep working, in both directions), but one HIP launch per step
-(dasac_sgd_step / dasac_sgd_nesterov_step / dasac_adam_step) instead of a chain of foreach passes per group."""
+(dasac_sgd_step / dasac_sgd_nesterov_step / dasac_adam_step) instead of a chain of foreach passes per group.
+
+Global gradient-norm clipping, norm logging and non-finite step skipping (`max_grad_norm`, `track_grad_norm`, `skip_nonfinite`)
+live here too, because with a stash `.grad` never holds the gradient that is applied: dasac_grad_norm measures stash + grad over
+the update's own table on the device, and the `_ctl` updates read its verdict from device memory -- no host synchronisation,
+no ATen arithmetic, three launches per step instead of one."""
 import ctypes
+import math
+import numbers
 
 import numpy as np
 import torch
@@ -18,12 +25,85 @@ class _FusedOptimizer(torch.optim.Optimizer):
     that have something to apply, and the upload of the per-step pointer table."""
     MAX_GROUPS = 8
 
-    def __init__(self, params, defaults):
+    def __init__(self, params, defaults, max_grad_norm=None, skip_nonfinite=False, track_grad_norm=False):
+        """The three keywords are attributes of the optimiser, not `param_groups` keys, and are not part of `state_dict()`
+        (groups and state keep torch's layout).
+        max_grad_norm: None, or a finite float > 0 -- the summed gradient of every step is scaled by
+            min(max_grad_norm / (norm + 1e-6), 1), norm = the global L2 norm of stash + grad over all parameters, as
+            `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` would scale `.grad` before the step.
+        track_grad_norm: measure that norm on every step without clipping (`grad_norm`).
+        skip_nonfinite: a step whose norm is Inf or NaN is skipped on the device.  A skipped step leaves parameters and
+            moment buffers untouched (FusedSGD fills a momentum buffer that the step would have created with -0.0, which
+            makes the next step exactly the first one: momentum * -0.0 + d is d for every d, where +0.0 would turn d = -0.0
+            into +0.0), clears the stash as usual and counts in `skipped_steps`.  The host does not learn
+            of it: version counters advance, and FusedAdam's `state[p]["step"]` advances too, so the bias corrections of later
+            steps are those of one step further on than the moments have seen.  Every rank of a data-parallel run holds the
+            same reduced gradients and therefore takes the same decision."""
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, numbers.Real) or not math.isfinite(max_grad_norm) \
+                    or not max_grad_norm > 0:
+                raise ValueError("{}: max_grad_norm must be None or a finite number > 0, got {!r}".format(type(self).__name__, max_grad_norm))
+            max_grad_norm = float(max_grad_norm)
         super().__init__(params, defaults)
         if len(self.param_groups) > self.MAX_GROUPS:
             raise ValueError("{}: at most {} parameter groups".format(type(self).__name__, self.MAX_GROUPS))
+        self.max_grad_norm, self.skip_nonfinite, self.track_grad_norm = max_grad_norm, bool(skip_nonfinite), bool(track_grad_norm)
         self._tables = {}            # slot -> (key, device tensor table, device chunk table, n_tensors, n_chunks)
         self._stash = {}             # parameter -> gradient of an earlier backward pass, summed inside the next step()
+        self._ctl = None             # device control blocks {total, coef, skip, reserved}: [0] of step(), [1] of measure_grad_norm()
+        self._skipped = None         # device int64 counter of skipped steps
+
+    def _controlled(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite or self.track_grad_norm
+
+    def _control(self):
+        if self._ctl is None:
+            p = self.param_groups[0]["params"][0]
+            L.require_gpu(p)
+            self._ctl = torch.zeros(2, 4, dtype=torch.float32, device=p.device)
+            self._skipped = torch.zeros((), dtype=torch.int64, device=p.device)
+        return self._ctl
+
+    @property
+    def grad_norm(self):
+        """0-dim fp32 device tensor: the global L2 norm of stash + grad that the last step() measured, before clipping (0 before
+        the first such step; Inf / NaN on a step that `skip_nonfinite` skipped).  A view of the control block: valid until the
+        next step().  Reading it does not synchronise."""
+        return self._control()[0, 0]
+
+    @property
+    def skipped_steps(self):
+        """0-dim int64 device tensor: how many steps `skip_nonfinite` has skipped.  Reading it does not synchronise."""
+        self._control()
+        return self._skipped
+
+    def measure_grad_norm(self):
+        """The global L2 norm of stash + grad as it stands -- what the next step() would measure -- as a new 0-dim fp32 device
+        tensor.  Updates nothing, leaves `.grad`, the stash and `grad_norm` alone, and does not synchronise: the device-side
+        stand-in for `clip_grad_norm_(full_grads().values(), inf)` when logging."""
+        # rows of the 48-byte table with only what the norm pass reads: g, g2 and n
+        pending = list(self._pending(peek=True))
+        rows = [(0, g.data_ptr(), 0 if g2 is None else g2.data_ptr(), 0, p.numel(), 0) for _, p, g, g2 in pending]
+        ctl = self._control()
+        if not rows:
+            return torch.zeros((), dtype=torch.float32, device=ctl.device)
+        key = tuple(v for r in rows for v in r)
+        _, tab, chunks, nt, nc = self._table("measure", key, np.asarray(rows, dtype=np.int64), [r[4] for r in rows], ctl.device)
+        self._norm_pass(tab, 48, nt, chunks, nc, ctl[1], 0.0, None)
+        return ctl[1, 0].clone()
+
+    def _norm_pass(self, tab, row_bytes, nt, chunks, nc, ctl, max_norm, skipped):
+        """dasac_grad_norm over an uploaded table into the control block `ctl`, on the current stream."""
+        lib = L.load()
+        ws = L.workspace(lib.dasac_grad_norm_workspace(nc), ctl.device)
+        L.check(lib.dasac_grad_norm(tab.data_ptr(), row_bytes, nt, chunks.data_ptr(), nc, float(max_norm), ws.data_ptr(), ws.numel(),
+                                    ctl.data_ptr(), L.ptr(skipped), L.stream_ptr()), "dasac_grad_norm")
+
+    def _step_norm_pass(self, tab, row_bytes, nt, chunks, nc):
+        """The norm pass of a controlled step; returns the tail of the `_ctl` update's arguments."""
+        ctl = self._control()[0]
+        self._norm_pass(tab, row_bytes, nt, chunks, nc, ctl, self.max_grad_norm or 0.0, self._skipped if self.skip_nonfinite else None)
+        return ctl.data_ptr(), int(self.max_grad_norm is not None), int(self.skip_nonfinite), L.stream_ptr()
 
     def stash_grads(self):
         """Sets the current gradients aside (p.grad becomes None): the next backward pass then ASSIGNS its gradients instead
@@ -54,21 +134,25 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._stash.clear()
         super().zero_grad(set_to_none=set_to_none)
 
-    def _pending(self):
+    def _pending(self, peek=False):
         """(group index, parameter, gradient, stashed gradient or None) of every parameter the next step() updates, checked
-        and made contiguous.  Nothing has been launched when this raises."""
+        and made contiguous.  Nothing has been launched when this raises.  peek: leave `.grad` as it is (a parameter that only
+        the stashed pass reached otherwise gets its stashed gradient back as `.grad`)."""
         name = type(self).__name__
         for gi, group in enumerate(self.param_groups):
             for p in group["params"]:
-                g2 = self._stash.get(p)
-                if p.grad is None:
+                g, g2 = p.grad, self._stash.get(p)
+                if g is None:
                     if g2 is None:
                         continue
-                    p.grad, g2 = g2, None            # only the stashed pass produced a gradient for this parameter
-                L.require_gpu(p, p.grad, g2)
-                if p.dtype != torch.float32 or not p.is_contiguous() or p.grad.is_sparse:
+                    g, g2 = g2, None                 # only the stashed pass produced a gradient for this parameter
+                    if not peek:
+                        p.grad = g
+                L.require_gpu(p, g, g2)
+                if p.dtype != torch.float32 or not p.is_contiguous() or g.is_sparse:
                     raise TypeError(name + ": dense contiguous fp32 parameters only")
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                if not g.is_contiguous():
+                    g = g.contiguous()
                 if g2 is not None and not g2.is_contiguous():
                     g2 = g2.contiguous()
                 yield gi, p, g, g2
@@ -92,13 +176,14 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
 
 class FusedSGD(_FusedOptimizer):
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, dampening=0.0):
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, nesterov=False, dampening=0.0, max_grad_norm=None,
+                 skip_nonfinite=False, track_grad_norm=False):
         if dampening != 0.0:
             raise NotImplementedError("FusedSGD: no dampening (the reference never sets it)")
         if nesterov and momentum <= 0:
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=bool(nesterov))
-        super().__init__(params, defaults)
+        super().__init__(params, defaults, max_grad_norm, skip_nonfinite, track_grad_norm)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -129,8 +214,21 @@ class FusedSGD(_FusedOptimizer):
         n = len(self.param_groups)
         lr, wd = self._group_floats("lr"), self._group_floats("weight_decay")
         entry, what = (lib.dasac_sgd_nesterov_step, "dasac_sgd_nesterov_step") if nesterov else (lib.dasac_sgd_step, "dasac_sgd_step")
+        if self._controlled():
+            # ONE table for the tensors that take their first step and those that do not (bit 32 of `group` tells them apart):
+            # the norm is a fact about all of them
+            both = [r[:5] + (r[5] | 1 << 32,) for r in rows[True]] + rows[False]
+            if both:
+                key = tuple(v for r in both for v in r)
+                _, tab, chunks, nt, nc = self._table("ctl", key, np.asarray(both, dtype=np.int64), [r[4] for r in both], device)
+                tail = self._step_norm_pass(tab, 48, nt, chunks, nc)
+                entry, what = (lib.dasac_sgd_nesterov_step_ctl, "dasac_sgd_nesterov_step_ctl") if nesterov else \
+                    (lib.dasac_sgd_step_ctl, "dasac_sgd_step_ctl")
+                L.check(entry(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(lr, ctypes.c_void_p),
+                              ctypes.cast(wd, ctypes.c_void_p), n, float(momentum), -1, *tail), what)
+            rows = {}
         for first in (True, False):
-            if not rows[first]:
+            if not rows.get(first):
                 continue
             key = tuple(v for r in rows[first] for v in r)
             _, tab, chunks, nt, nc = self._table(first, key, np.asarray(rows[first], dtype=np.int64), [r[4] for r in rows[first]], device)
@@ -143,17 +241,19 @@ class FusedSGD(_FusedOptimizer):
 
 class FusedAdam(_FusedOptimizer):
     """torch.optim.Adam as the reference builds it: L2 weight decay added to the gradient, no amsgrad.  `state[p]` holds
-    `step` (a host fp32 tensor, as torch keeps it), `exp_avg` and `exp_avg_sq`; the group keys are torch.optim.Adam's."""
+    `step` (a host fp32 tensor, as torch keeps it), `exp_avg` and `exp_avg_sq`; the group keys are torch.optim.Adam's.
+    Under `skip_nonfinite` a skipped step leaves `exp_avg` / `exp_avg_sq` alone but still advances the host-side `step`: the
+    bias corrections are then one step ahead of the moments (see _FusedOptimizer.__init__)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
-                 capturable=False):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False, track_grad_norm=False):
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay:
             raise ValueError("FusedAdam: lr, eps and weight_decay must not be negative")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("FusedAdam: betas must lie in [0, 1)")
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None,
                         capturable=capturable, differentiable=False, fused=None, decoupled_weight_decay=False)
-        super().__init__(params, defaults)
+        super().__init__(params, defaults, max_grad_norm, skip_nonfinite, track_grad_norm)
         self._hyper()
 
     def _hyper(self):
@@ -205,8 +305,13 @@ class FusedAdam(_FusedOptimizer):
             key = tuple(v for r in ptrs for v in r) + tuple(v for r in scalars for v in r)
             _, tab, chunks, nt, nc = self._table(0, key, rows, [r[5] for r in ptrs], device)
             wd = self._group_floats("weight_decay")
-            L.check(lib.dasac_adam_step(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(wd, ctypes.c_void_p),
-                                        len(self.param_groups), beta1, beta2, eps, L.stream_ptr()), "dasac_adam_step")
+            if self._controlled():
+                tail = self._step_norm_pass(tab, 64, nt, chunks, nc)
+                L.check(lib.dasac_adam_step_ctl(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(wd, ctypes.c_void_p),
+                                                len(self.param_groups), beta1, beta2, eps, *tail), "dasac_adam_step_ctl")
+            else:
+                L.check(lib.dasac_adam_step(tab.data_ptr(), nt, chunks.data_ptr(), nc, ctypes.cast(wd, ctypes.c_void_p),
+                                            len(self.param_groups), beta1, beta2, eps, L.stream_ptr()), "dasac_adam_step")
             ops.bump_versions(touched)   # raw-pointer writes: keep autograd's version counters (engine cache keys) honest
         self._stash.clear()
         return loss

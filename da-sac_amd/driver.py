@@ -5,7 +5,7 @@ DistributedDataParallel wrapper (backend "nccl" == RCCL on ROCm)."""
 import torch
 
 
-def make_optimizer(net, cfg_model, fused=True):
+def make_optimizer(net, cfg_model, fused=True, max_grad_norm=None, skip_nonfinite=False):
     """`BaseTrainer.get_optim` (base_trainer.py:47-73) over the model's four parameter groups (train.py:93-96):
       OPT == "SGD" (the default, configs/*.yaml): SGD(momentum, nesterov=OPT_NESTEROV) -- the fused multi-tensor HIP optimiser
           (same update rule / state layout) for plain momentum or, with fused=False / nesterov, torch.optim.SGD itself;
@@ -13,6 +13,10 @@ def make_optimizer(net, cfg_model, fused=True):
       any other name in torch.optim: optim(params, lr=LR) (base_trainer.py:68-69); unknown names raise NotImplementedError.
     fused="all" also returns the HIP optimisers for the other two cases of the factory: `FusedSGD(nesterov=True)` under
     OPT_NESTEROV and `FusedAdam` under OPT == "Adam" (anything else as under fused=True).
+    max_grad_norm / skip_nonfinite: global L2 gradient-norm clipping and skipping of a step whose gradient norm is Inf / NaN,
+    inside the fused optimisers (dasac_hip/optim.py; `optim.grad_norm` and `optim.skipped_steps` are device tensors).  Either
+    one implies fused="all", so that all three cases of the factory have it; ValueError with fused=False or an OPT that has no
+    fused class.
     Every group carries its own lr / weight_decay (basenet.py:102-139), so the keyword defaults below only fill the gaps,
     exactly as in the reference."""
     core = net.module if hasattr(net, "module") else net
@@ -21,19 +25,25 @@ def make_optimizer(net, cfg_model, fused=True):
     if not hasattr(torch.optim, opt):
         print("Optimiser {} not supported".format(opt))
         raise NotImplementedError
+    guard = {}
+    if max_grad_norm is not None or skip_nonfinite:
+        if not fused or opt not in ("SGD", "Adam"):
+            raise ValueError("max_grad_norm / skip_nonfinite live in the fused optimisers: not with fused=False or OPT == {!r}".format(opt))
+        fused, guard = "all", dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     fuse_all = isinstance(fused, str) and fused == "all"
     if opt == "Adam":
         betas = (getattr(cfg_model, "BETA1", 0.5), 0.999)
         if fuse_all:
             from dasac_hip.optim import FusedAdam
-            upd = FusedAdam(groups, lr=cfg_model.LR, betas=betas, weight_decay=cfg_model.WEIGHT_DECAY)
+            upd = FusedAdam(groups, lr=cfg_model.LR, betas=betas, weight_decay=cfg_model.WEIGHT_DECAY, **guard)
         else:
             upd = torch.optim.Adam(groups, lr=cfg_model.LR, betas=betas, weight_decay=cfg_model.WEIGHT_DECAY)
     elif opt == "SGD":
         nesterov = getattr(cfg_model, "OPT_NESTEROV", False)
         if fused and (fuse_all or not nesterov):
             from dasac_hip.optim import FusedSGD
-            upd = FusedSGD(groups, lr=cfg_model.LR, momentum=cfg_model.MOMENTUM, weight_decay=cfg_model.WEIGHT_DECAY, nesterov=nesterov)
+            upd = FusedSGD(groups, lr=cfg_model.LR, momentum=cfg_model.MOMENTUM, weight_decay=cfg_model.WEIGHT_DECAY, nesterov=nesterov,
+                           **guard)
         else:
             upd = torch.optim.SGD(groups, lr=cfg_model.LR, momentum=cfg_model.MOMENTUM, nesterov=nesterov, weight_decay=cfg_model.WEIGHT_DECAY)
     else:
@@ -138,9 +148,11 @@ def sac_train_iteration(net, optim, src_batch, tgt_batch, group_size, update_tea
     ResNet-101).  With a fused optimiser (`FusedSGD`, plain or Nesterov, and `FusedAdam`: anything that has `stash_grads`) the
     source gradients are set aside instead and the update kernel applies
     source + target -- on one rank the same sum, bit for bit.  Between the target backward and step(), and after it,
-    `.grad` holds the target-pass gradient only: anything that reads gradients before the step (clipping, norm logging)
-    must use `optim.full_grads()` or pass sum_grads_in_optimizer=False (or another optimiser) for the reference's `.grad`
-    contents.  Under data parallelism the update is mean_r(src_r) + mean_r(tgt_r) where the reference's DDP reduces
+    `.grad` holds the target-pass gradient only: clipping and norm logging therefore happen inside the fused optimisers
+    (`make_optimizer(..., max_grad_norm=, skip_nonfinite=)`, `optim.grad_norm`, `optim.measure_grad_norm()`: the norm of
+    source + target, measured on the device); anything else that reads gradients before the step can use `optim.full_grads()`
+    or pass sum_grads_in_optimizer=False (or another optimiser) for the reference's `.grad` contents.
+    Under data parallelism the update is mean_r(src_r) + mean_r(tgt_r) where the reference's DDP reduces
     mean_r(mean(src) + tgt_r): equal in exact arithmetic, one rounding apart in fp32 (not bit-identical) -- for every fused
     optimiser alike.
 

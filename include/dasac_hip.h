@@ -314,6 +314,35 @@ int dasac_sgd_nesterov_step(const void* tensors, int n_tensors, const int32_t* c
 int dasac_adam_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
                     const float* group_wd, int n_groups, double beta1, double beta2, double eps,
                     dasac_stream_t stream);
+/* Global L2 gradient-norm clipping and non-finite step skipping for the three updates above, without a host synchronisation.
+ * dasac_grad_norm reads g, g2 and n from the SAME uploaded table the update reads (row_bytes names it: 48 = the rows of
+ * dasac_sgd_step, 64 = those of dasac_adam_step) over the same chunks, and writes the 16-byte device control block
+ *   ctl = {float total; float coef; int32 skip; int32 reserved}
+ *   total = (float)sqrt(sum over all elements of (g2 + g)^2): the fp32 sum the update applies, squared and added in double, one
+ *           partial per chunk in `workspace` (dasac_grad_norm_workspace(n_chunks) bytes), no atomics, partials added in a fixed
+ *           order: the same inputs give the same bits, wherever the gradients lie (16-byte loads or not);
+ *   coef  = min(max_norm / (total + 1e-6f), 1.0f) in fp32 as torch.nn.utils.clip_grad_norm_ forms it (NaN stays NaN), or
+ *           1.0f with max_norm <= 0 (measure only);
+ *   skip  = total is not finite.
+ * `skipped` (NULL, or a device int64 counter) grows by `skip`.  ctl must be 16-byte aligned.
+ * The _ctl updates are the plain ones plus: apply_coef = 1 multiplies the summed gradient by ctl->coef (one fp32 multiply,
+ * before weight decay); honour_skip = 1 makes the launch write nothing while ctl->skip is set -- except that a FIRST SGD step
+ * writes buf = -0, so that the next step's momentum*buf + d is the first-step rule without the host knowing.  The SGD forms
+ * also take first = -1: bit 32 of each row's `group` then says whether that tensor takes its first step (one table, hence
+ * one norm, for a step in which some tensors are new); `group` itself is bits 0-2. */
+size_t dasac_grad_norm_workspace(int n_chunks);
+int dasac_grad_norm(const void* tensors, int row_bytes, int n_tensors, const int32_t* chunks, int n_chunks,
+                    float max_norm, void* workspace, size_t workspace_bytes, void* ctl, int64_t* skipped,
+                    dasac_stream_t stream);
+int dasac_sgd_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                       const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
+                       const void* ctl, int apply_coef, int honour_skip, dasac_stream_t stream);
+int dasac_sgd_nesterov_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                                const float* group_lr, const float* group_wd, int n_groups, float momentum,
+                                int first, const void* ctl, int apply_coef, int honour_skip, dasac_stream_t stream);
+int dasac_adam_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
+                        const float* group_wd, int n_groups, double beta1, double beta2, double eps,
+                        const void* ctl, int apply_coef, int honour_skip, dasac_stream_t stream);
 int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks,
                      float momentum, int update, double* sq, float* out, dasac_stream_t stream);
 int dasac_scale_planes(const float* x, const float* plane_scale, int64_t planes, int64_t HW,
