@@ -35,6 +35,8 @@ PROTOTYPES = {
     "dasac_conv_wgrad_x3": (_i, [_p, _p, _p] + [_i] * 9 + [_p, _sz, _p]),
     "dasac_upsample_softmax": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dasac_infer_labels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "dasac_image_pyramid": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "dasac_infer_fuse": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dasac_upsample_bwd_workspace": (_sz, [_i, _i, _i]),
     "dasac_upsample_bwd": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "dasac_ce_loss_workspace": (_sz, [_i, _i, _l]),
@@ -106,6 +108,11 @@ class VisJob(C.Structure):
     """`dasac_vis_job` of include/dasac_hip.h (48 bytes)."""
     _fields_ = [("src", _p), ("backdrop", _p), ("kind", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
                 ("softmax", C.c_int32), ("column", C.c_int32), ("column2", C.c_int32), ("reserved", C.c_int32)]
+
+
+class InferSource(C.Structure):
+    """`dasac_infer_source` of include/dasac_hip.h (24 bytes)."""
+    _fields_ = [("logits", _p), ("h", C.c_int32), ("w", C.c_int32), ("flip", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DasacError(RuntimeError):

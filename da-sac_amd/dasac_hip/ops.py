@@ -372,6 +372,62 @@ def infer_labels(logits, size, lut=None, want_conf=False):
     return labels, conf
 
 
+INFER_MAX_SOURCES = 8                       # DASAC_INFER_MAX_SOURCES
+INFER_MODES = {"mean": 0, "max": 1}         # DASAC_INFER_MEAN / DASAC_INFER_MAX
+
+
+def image_pyramid(image, size, flip=False):
+    """F.interpolate(image, size, mode="bilinear", align_corners=True) of a float32 [B,Cin,H,W] image in one launch; with `flip`
+    the result is [2B,Cin,Hs,Ws] and rows B..2B-1 are the horizontally mirrored copies (`.flip(-1)`, bit for bit).  size ==
+    (H, W) is legal: the plain half then equals the input."""
+    lib = L.load()
+    L.require_gpu(image)
+    if image.dtype != torch.float32 or image.dim() != 4:
+        raise L.DasacError("image_pyramid takes a float32 [B,Cin,H,W] image (got {} {})".format(image.dtype, tuple(image.shape)))
+    image = _c(image)
+    B, Cin, H, W = image.shape
+    Hs, Ws = int(size[0]), int(size[1])
+    out = torch.empty((2 * B if flip else B, Cin, Hs, Ws), dtype=torch.float32, device=image.device)
+    L.check(lib.dasac_image_pyramid(image.data_ptr(), B, Cin, H, W, Hs, Ws, int(bool(flip)), out.data_ptr(), L.stream_ptr()),
+            "dasac_image_pyramid")
+    return out
+
+
+def infer_fuse(sources, flips, size, mode="mean", lut=None, want_conf=False, want_probs=False):
+    """Multi-scale / mirrored inference in ONE kernel: `sources` are up to 8 float32 logit tensors [B,C,h_s,w_s] (sizes may
+    differ), `flips[s]` says that source s was computed from the horizontally mirrored image.  Per output pixel of `size`:
+    softmax(bilinear_ac(source)) per source (a flipped one read at the mirrored column), mean or max over the sources, argmax.
+    Returns (labels u8 [B,H,W] through `lut` if given, conf f32 [B,H,W] or None, probs f32 [B,C,H,W] or None).  A source may be
+    a batch slice of a larger contiguous tensor (the mirrored half of a 2B-batch backbone call)."""
+    import ctypes as C
+    lib = L.load()
+    sources, flips = list(sources), list(flips)
+    L.require_gpu(lut, *sources)
+    if mode not in INFER_MODES:
+        raise L.DasacError("infer_fuse: mode must be one of {} (got {!r})".format(sorted(INFER_MODES), mode))
+    if not sources or len(flips) != len(sources):
+        raise L.DasacError("infer_fuse takes at least one source and one flip flag per source (got {} and {})".format(
+            len(sources), len(flips)))
+    B, Cn = sources[0].shape[:2]
+    for s in sources:
+        if s.dtype != torch.float32 or s.dim() != 4 or tuple(s.shape[:2]) != (B, Cn):
+            raise L.DasacError("infer_fuse: every source must be float32 [{},{},h,w] (got {} {})".format(B, Cn, s.dtype, tuple(s.shape)))
+    sources = [_c(s) for s in sources]
+    H, W = int(size[0]), int(size[1])
+    device = sources[0].device
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=device)
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=device) if want_conf else None
+    probs = torch.empty((B, Cn, H, W), dtype=torch.float32, device=device) if want_probs else None
+    if lut is not None:
+        assert lut.dtype == torch.uint8 and lut.numel() >= Cn and lut.is_contiguous()
+    table = (L.InferSource * len(sources))()
+    for i, (s, f) in enumerate(zip(sources, flips)):
+        table[i] = L.InferSource(s.data_ptr(), s.shape[2], s.shape[3], int(bool(f)), 0)
+    L.check(lib.dasac_infer_fuse(C.cast(table, C.c_void_p), len(sources), B, Cn, H, W, INFER_MODES[mode], L.ptr(lut),
+                                 labels.data_ptr(), L.ptr(conf), L.ptr(probs), L.stream_ptr()), "dasac_infer_fuse")
+    return labels, conf, probs
+
+
 def upsample_bwd(grad_up, low_hw, gscale=None):
     lib = L.load()
     L.require_gpu(grad_up, gscale)

@@ -385,20 +385,87 @@ def infer_label_maps(net, image, lut=None, teacher=False, want_conf=False):
         return ops.infer_labels(logits, image.shape[-2:], lut, want_conf)
 
 
-def validation_iou(net, batches, num_classes=19):
+INFER_MS_MAX_SOURCES = 8                     # ops.INFER_MAX_SOURCES: what one infer_fuse launch takes
+
+
+def scaled_size(H, W, scale):
+    """The size rule of the multi-scale path: (int(H * s + 0.5), int(W * s + 0.5))."""
+    return int(H * scale + 0.5), int(W * scale + 0.5)
+
+
+def _ms_plan(H, W, scales, flip):
+    """[(Hs, Ws, needs_pyramid)] per scale; ValueError for no scale, too many sources or a scale that leaves no pixel."""
+    scales = tuple(float(s) for s in scales)
+    if not scales:
+        raise ValueError("infer_label_maps_ms: no scale given")
+    n_sources = len(scales) * (2 if flip else 1)
+    if n_sources > INFER_MS_MAX_SOURCES:
+        raise ValueError("infer_label_maps_ms: {} scales{} make {} sources; one launch takes {}".format(
+            len(scales), " x 2 orientations" if flip else "", n_sources, INFER_MS_MAX_SOURCES))
+    plan = []
+    for s in scales:
+        Hs, Ws = scaled_size(H, W, s)
+        if Hs < 1 or Ws < 1:
+            raise ValueError("infer_label_maps_ms: scale {} of a {}x{} image gives {}x{}".format(s, H, W, Hs, Ws))
+        plan.append((Hs, Ws, flip or s != 1.0))
+    return plan
+
+
+def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="mean", lut=None, teacher=False, want_conf=False,
+                        want_probs=False):
+    """infer_label_maps with test-time augmentation: the image at every scale of `scales`, plain and (with `flip`) mirrored, the
+    class probabilities of all of them fused by mean or max (`mode`) at the image's own size.  Per scale s the backbone sees
+    scaled_size(H, W, s) pixels: ONE ops.image_pyramid launch makes the scaled (and mirrored) input -- none for s == 1.0 without
+    flip, the image itself is passed -- and ONE `_logits` call runs it, at batch 2B when flipping; then ONE ops.infer_fuse launch
+    over all the halves (the mirrored half is a batch slice of the same logits tensor) writes the uint8 label map.  No
+    upsampled, flipped, softmaxed or summed [B,C,H,W] tensor exists; torch only allocates.  At most 8 sources (scales x
+    orientations).  Returns (labels u8 [B,H,W], conf f32 [B,H,W] or None, probs f32 [B,C,H,W] or None): conf is the winning fused
+    probability, probs all of them (infer_val.py's D_SAVE_RAW).  `lut`, `teacher` as infer_label_maps."""
+    from dasac_hip import ops
+    B, _, H, W = image.shape
+    plan = _ms_plan(H, W, scales, flip)
+    core = net.module if hasattr(net, "module") else net
+    backbone = core
+    if hasattr(core, "backbone"):
+        backbone = core.slow_net if teacher else core.backbone
+    if lut is not None and not torch.is_tensor(lut):
+        lut = torch.tensor(list(lut), dtype=torch.uint8, device=image.device)
+    sources, flips = [], []
+    with torch.no_grad():
+        for Hs, Ws, resample in plan:
+            logits = backbone._logits(ops.image_pyramid(image, (Hs, Ws), flip) if resample else image)
+            sources.append(logits[:B])
+            flips.append(False)
+            if flip:
+                sources.append(logits[B:])
+                flips.append(True)
+        return ops.infer_fuse(sources, flips, (H, W), mode, lut, want_conf, want_probs)
+
+
+def validation_iou(net, batches, num_classes=19, scales=None, flip=False):
     """mIoU over (image, label) batches: argmax + per-class tp/fp/fn in one kernel pass per batch
-    (train.py:339-469, utils/metrics.py:9-53); counts are all-reduced when a process group exists."""
+    (train.py:339-469, utils/metrics.py:9-53); counts are all-reduced when a process group exists.
+    With `scales` (or `flip`) the prediction is infer_label_maps_ms's label map (scales defaults to (1.0,) when only `flip` is
+    set) and the counts come from the label-layer counter (ops.mask_counts, as `validation` counts `teacher_labels`); the uint8
+    map is widened to the int64 that counter reads, the one torch operation of that path."""
     import torch.distributed as dist
     from dasac_hip import ops
     core = net.module if hasattr(net, "module") else net
     was = core.training
     core.eval()
     counts = None
+    multi_scale = scales is not None or flip
     with torch.no_grad():
         for image, gt in batches:
-            _, logits_up = core(image)
-            counts = ops.iou_counts(logits_up, gt, counts)
+            if multi_scale:
+                maps, _, _ = infer_label_maps_ms(net, image, (1.0,) if scales is None else scales, flip)
+                counts = ops.mask_counts([], [maps.to(torch.int64)], gt, counts, num_classes=num_classes)
+            else:
+                _, logits_up = core(image)
+                counts = ops.iou_counts(logits_up, gt, counts)
     core.train(was)
+    if multi_scale and counts is not None:
+        counts = counts[0]
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(counts)
     iou, _, _ = summarise_iou(counts)
@@ -413,7 +480,7 @@ def summarise_iou(counts):
     return tp / torch.maximum(floor, fn + fp + tp), tp / torch.maximum(floor, tp + fp), tp / torch.maximum(floor, tp + fn)
 
 
-def compute_sample_weights(net, batches, num_images, lut=None, teacher=False):
+def compute_sample_weights(net, batches, num_images, lut=None, teacher=False, scales=None, flip=False):
     """Stage 2 of the reference's schedule (tools/compute_IS_weights.py on the masks infer_val.py wrote) without leaving the
     device: per-image class pixel counts of the network's label maps, int64 [num_images,256] on the host -- the input of
     sampling.weights_from_counts.  `batches` yields (image [B,3,H,W] on the device, global image indices [B] as a HOST
@@ -421,7 +488,8 @@ def compute_sample_weights(net, batches, num_images, lut=None, teacher=False):
     run of consecutive indices, with no host synchronisation inside the loop and one D2H copy at the end.  The network runs
     in eval mode.  With a process group of world > 1 each rank passes its own slice of the images and the tables are summed
     over ranks; a row no rank touched stays zero.  `lut` as infer_label_maps (e.g. CITYSCAPES_TRAIN_TO_ID: the counts land
-    in the Cityscapes-id bins)."""
+    in the Cityscapes-id bins).  With `scales` (or `flip`) the label maps are infer_label_maps_ms's (scales defaults to (1.0,)
+    when only `flip` is set)."""
     import torch.distributed as dist
     from dasac_hip import ops
     core = net.module if hasattr(net, "module") else net
@@ -431,7 +499,10 @@ def compute_sample_weights(net, batches, num_images, lut=None, teacher=False):
     for image, index in batches:
         index = [int(i) for i in (index.tolist() if torch.is_tensor(index) else index)]
         assert len(index) == image.shape[0] and all(0 <= i < num_images for i in index), (index, num_images)
-        maps, _ = infer_label_maps(net, image, lut, teacher)
+        if scales is not None or flip:
+            maps = infer_label_maps_ms(net, image, (1.0,) if scales is None else scales, flip, lut=lut, teacher=teacher)[0]
+        else:
+            maps, _ = infer_label_maps(net, image, lut, teacher)
         lo = 0
         for hi in range(1, len(index) + 1):
             if hi == len(index) or index[hi] != index[hi - 1] + 1:

@@ -245,6 +245,32 @@ int dasac_ce_loss_bwd_low(const float* logits_up, const int64_t* labels, const f
  * conf = the winning probability.  1 (+4) bytes written per output pixel. */
 int dasac_infer_labels(const float* logits, int B, int C, int h, int w, int H, int W, const uint8_t* lut,
                        uint8_t* labels, float* conf, dasac_stream_t stream);
+/* Test-time augmentation around it (infer_val.py is single-scale; the usual evaluation form runs the image at a few scales,
+ * plain and mirrored, and averages the class probabilities).
+ * dasac_image_pyramid  out[0:B] = F.interpolate(image [B,Cin,H,W], (Hs, Ws), bilinear, align_corners=True); with_flip: out is
+ *     [2B,Cin,Hs,Ws] and out[B:2B] = out[0:B].flip(-1), bit for bit (the same thread writes both: one read of the source).
+ *     The source coordinate dst*(n_in-1)/(n_out-1) is taken in integers (quotient = tap, remainder/(n_out-1) = weight), so the
+ *     result is within fp32 rounding of the float64 interpolate at any scale.  Hs*H and Ws*W < 2^31.
+ *     Hs == H && Ws == W is legal: the weights are exactly (1, 0) and out[0:B] == image.  B*Cin < 65536.
+ * dasac_infer_fuse     dasac_infer_labels over n_sources <= DASAC_INFER_MAX_SOURCES logit tensors [B,C,h_s,w_s] in ONE pass
+ *     per output pixel:  p_s = softmax_c(bilinear_ac(logits_s))[b,:,y, flip_s ? W-1-x : x]  (= interpolate(.).flip(-1) for a
+ *     source computed from the mirrored image), same arithmetic per source as dasac_infer_labels;
+ *     fused = (p_0 + p_1 + ...) * (1.f / n) in source order (DASAC_INFER_MEAN) or max_s p_s (DASAC_INFER_MAX);
+ *     labels u8 [B,H,W] = lut[argmax_c fused] (first maximum wins; lut NULL: the class index), conf f32 [B,H,W] (optional) = the
+ *     winning fused value, probs f32 [B,C,H,W] (optional) = all of them (what infer_val.py's D_SAVE_RAW stores).
+ *     `sources` is a HOST array; its records travel to the kernel by value: no device table, no workspace.  One unflipped
+ *     source gives dasac_infer_labels' bits.  C <= 32.  1 (+4) (+4C) bytes written per output pixel. */
+#define DASAC_INFER_MAX_SOURCES 8
+#define DASAC_INFER_MEAN 0
+#define DASAC_INFER_MAX 1
+typedef struct dasac_infer_source {
+  const float* logits; /* device, [B,C,h,w] */
+  int32_t h, w, flip, reserved;
+} dasac_infer_source;
+int dasac_image_pyramid(const float* image, int B, int Cin, int H, int W, int Hs, int Ws, int with_flip, float* out,
+                        dasac_stream_t stream);
+int dasac_infer_fuse(const dasac_infer_source* sources, int n_sources, int B, int C, int H, int W, int mode,
+                     const uint8_t* lut, uint8_t* labels, float* conf, float* probs, dasac_stream_t stream);
 int dasac_warp_affine(const float* x, const float* theta, int B, int C, int H, int W, float* out,
                       dasac_stream_t stream);
 int dasac_warp_pool(const float* probs, const float* theta, const float* theta_inv, int N, int T,
