@@ -9,6 +9,8 @@
 //   warp_back          models/sac.py:309-311
 //   warp_affine        models/sac.py:295-296 (diagnostic frame warp)
 //   class_state        models/sac.py:104-117,120,151-152                  running class prior, discount, focal weights
+// The bilinear taps (tap_ac / ac_scale) are bilinear.hpp's; the inference label map (dasac_infer_labels) is in inference.hip.
+#include "bilinear.hpp"
 #include "common.hpp"
 
 #include <algorithm>
@@ -22,23 +24,6 @@ constexpr int kMaxC = 32;   // classes held in registers
 constexpr int kHB = 256;
 constexpr float kQ32 = 4294967296.f;     // fixed-point scales of the order-independent (integer) reductions
 constexpr float kQ28 = 268435456.f;
-
-// ---- bilinear taps, align_corners=True (ATen upsample_bilinear2d: src = scale*dst) ----------
-struct Tap {
-  int i0, i1;
-  float w0, w1;
-};
-__host__ __device__ __forceinline__ Tap tap_ac(int dst, float scale, int n_in) {
-  const float src = scale * (float)dst;
-  int i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
-  Tap t;
-  t.i0 = i0;
-  t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  t.w1 = src - (float)i0;
-  t.w0 = 1.f - t.w1;
-  return t;
-}
 
 // scalar base + 32-bit per-lane byte offset: the form the global_load / global_store saddr encoding takes without any VALU
 __device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
@@ -221,57 +206,6 @@ __global__ void q32_to_double(unsigned long long* __restrict__ q, int C) {
   if (c >= C) return;
   const unsigned long long v = q[c];
   reinterpret_cast<double*>(q)[c] = (double)v * (1.0 / 4294967296.0);
-}
-
-// ---- inference (infer_val.py:160-163 + the writer's argmax / trainId->labelId LUT, :60-65): bilinear(ac=True) +
-// softmax + argmax + LUT in one pass over the low-resolution logits; writes 1 byte (+ optional confidence) per
-// high-resolution pixel instead of two [C,H,W] fp32 tensors.  Same per-pixel arithmetic as upsample_softmax.
-template <int CT>
-__global__ __launch_bounds__(kHB) void infer_labels(const float* __restrict__ x, int Crt, int h, int w, int H, int W, float sh,
-                                                    float sw, const uint8_t* __restrict__ lut, uint8_t* __restrict__ labels,
-                                                    float* __restrict__ conf, int blocks_per_image) {
-  const int C = CT < kMaxC ? CT : Crt;
-  const int b = blockIdx.x / blocks_per_image, chunk = blockIdx.x % blocks_per_image;
-  const int HW = H * W, hw = h * w;
-  const float* xb = x + (size_t)b * C * hw;
-  for (int p = chunk * kHB + threadIdx.x; p < HW; p += blocks_per_image * kHB) {
-    const int oy = p / W, ox = p - oy * W;
-    const Tap ty = tap_ac(oy, sh, h), tx = tap_ac(ox, sw, w);
-    const int o00 = ty.i0 * w + tx.i0, o01 = ty.i0 * w + tx.i1, o10 = ty.i1 * w + tx.i0, o11 = ty.i1 * w + tx.i1;
-    float v[CT];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      if (c < C) {
-        const float* pl = xb + (size_t)c * hw;
-        const float top = tx.w0 * pl[o00] + tx.w1 * pl[o01];
-        const float bot = tx.w0 * pl[o10] + tx.w1 * pl[o11];
-        v[c] = ty.w0 * top + ty.w1 * bot;
-        mx = fmaxf(mx, v[c]);
-      }
-    }
-    float den = 0.f;
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-      if (c < C) {
-        v[c] = expf(v[c] - mx);
-        den += v[c];
-      }
-    const float inv = 1.f / den;
-    int best = 0;
-    float bp = -1.f;
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-      if (c < C) {
-        const float pr = v[c] * inv;
-        if (pr > bp) {             // strict: the first maximum wins, as torch.argmax / numpy.argmax
-          bp = pr;
-          best = c;
-        }
-      }
-    labels[(size_t)b * HW + p] = lut ? lut[best] : (uint8_t)best;
-    if (conf) conf[(size_t)b * HW + p] = bp;
-  }
 }
 
 // ---- transpose of the bilinear upsampling, separable and gather-based (deterministic) ---------
@@ -1173,8 +1107,6 @@ __global__ void class_state(float* __restrict__ chi, const double* __restrict__ 
 
 using namespace dasac;
 
-static float ac_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
-
 extern "C" int dasac_upsample_softmax(const float* logits, int B, int C, int h, int w, int H, int W,
                                       const uint8_t* ignore, float* up, float* probs, double* class_sums,
                                       dasac_stream_t stream) {
@@ -1210,22 +1142,6 @@ extern "C" int dasac_upsample_softmax(const float* logits, int B, int C, int h, 
     hipLaunchKernelGGL(q32_to_double, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned long long*>(class_sums), C);
     DASAC_CHECK_LAUNCH("q32_to_double");
   }
-  return DASAC_OK;
-}
-
-extern "C" int dasac_infer_labels(const float* logits, int B, int C, int h, int w, int H, int W, const uint8_t* lut,
-                                  uint8_t* labels, float* conf, dasac_stream_t stream) {
-  DASAC_REQUIRE(logits && labels, "infer_labels: null pointer");
-  DASAC_REQUIRE(B > 0 && C > 0 && C <= kMaxC && h > 0 && w > 0 && H > 0 && W > 0, "infer_labels: bad shape");
-  const int per = stream_grid((int64_t)H * W, kHB, (kNumCu * 16 + B - 1) / B);
-  hipStream_t s = as_stream(stream);
-  if (C == 19)
-    hipLaunchKernelGGL(infer_labels<19>, dim3(per * B), dim3(kHB), 0, s, logits, C, h, w, H, W, ac_scale(h, H), ac_scale(w, W), lut,
-                       labels, conf, per);
-  else
-    hipLaunchKernelGGL(infer_labels<kMaxC>, dim3(per * B), dim3(kHB), 0, s, logits, C, h, w, H, W, ac_scale(h, H), ac_scale(w, W), lut,
-                       labels, conf, per);
-  DASAC_CHECK_LAUNCH("infer_labels");
   return DASAC_OK;
 }
 

@@ -4,17 +4,17 @@
 //   image_pyramid   the scaled (and mirrored) copies of a normalised image that the backbone runs on: bilinear,
 //                   align_corners=True, [B,Cin,H,W] -> [B or 2B,Cin,Hs,Ws]; the mirrored half is written by the thread that
 //                   computed the plain value, so one launch is one read of the source and the halves agree bit for bit.
-//   infer_fuse      infer_labels of head.hip over S <= 8 low-resolution logit tensors at once: per output pixel and source the
-//                   bilinear taps (at the mirrored column for a source that saw the mirrored image: interpolate(x).flip(-1)),
-//                   the max-subtracted softmax, then mean or max over the sources, argmax (first maximum wins), LUT.  Writes
-//                   1 byte per pixel (+ 4 for the confidence, + 4 C for the fused probabilities); none of the S upsampled
-//                   [B,C,H,W] tensors, their flips, softmaxes or running sum ever exists.
+//   infer_fuse      the label-map kernel (infer_val.py:160-163 + the writer's argmax / trainId->labelId LUT, :60-65) over
+//                   S <= 8 low-resolution logit tensors at once: per output pixel and source the bilinear taps (at the mirrored
+//                   column for a source that saw the mirrored image: interpolate(x).flip(-1)), the max-subtracted softmax, then
+//                   mean or max over the sources, argmax (first maximum wins), LUT.  Writes 1 byte per pixel (+ 4 for the
+//                   confidence, + 4 C for the fused probabilities); none of the S upsampled [B,C,H,W] tensors, their flips,
+//                   softmaxes or running sum ever exists.  dasac_infer_labels is this kernel over one unflipped source.
 //
-// Tap arithmetic: ATen's align_corners=True weights, tap_ac / ac_scale of head.hip restated (as visualise.hip does), with the
-// operations in the same order -- a single unflipped source gives infer_labels' bits.  image_pyramid takes the same taps from
+// Tap arithmetic: ATen's align_corners=True weights, tap_ac / ac_scale of bilinear.hpp.  image_pyramid takes the same taps from
 // integers instead (pyr_tap): the fp32 product scale * dst is off by up to ~2e-6 pixels at an inexact scale (37 -> 46 rows is
 // 0.8), which times the pixel-to-pixel difference of an image is a few 1e-6 of its range -- more than a pointwise kernel may
-// differ from float64.  The logits that infer_fuse reads are smooth by comparison and are held to infer_labels' bits.
+// differ from float64.  The logits that infer_fuse reads are smooth by comparison.
 //
 // Shape of infer_fuse: one pixel per thread, v[CT] (this source) and acc[CT] (fused) in registers.  Four pixels per thread, as
 // in upsample_softmax, buys that kernel dwordx4 stores of its 76 B per pixel and shared taps at the fixed 8x factor; here the
@@ -23,6 +23,7 @@
 // kernel whose time is gathers from L2 and expf, i.e. latency that wants waves (head.hip's round-4 note measured the same
 // trade going the same way at two pixels per thread).  The source loop is a runtime loop over a by-value argument struct
 // (wave-uniform scalar loads), not unrolled: S x 19 taps in flight would cost the registers that the occupancy needs.
+#include "bilinear.hpp"
 #include "common.hpp"
 
 #include <climits>
@@ -30,33 +31,16 @@
 namespace dasac {
 
 constexpr int kInfB = 256;
-constexpr int kInfMaxC = 32;   // classes held in registers (kMaxC of head.hip)
-
-struct InfTap {
-  int i0, i1;
-  float w0, w1;
-};
-__device__ __forceinline__ InfTap inf_tap(int dst, float scale, int n_in) {
-  const float src = scale * (float)dst;
-  int i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
-  InfTap t;
-  t.i0 = i0;
-  t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  t.w1 = src - (float)i0;
-  t.w0 = 1.f - t.w1;
-  return t;
-}
-static float inf_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
+constexpr int kInfMaxC = 32;   // classes held in registers
 
 // src = dst * (n_in - 1) / (n_out - 1) exactly: i0 the quotient, w1 the remainder over the divisor (one rounding).  den =
 // max(n_out - 1, 1), div = fast_div(den); dst * (n_in - 1) < 2^31 is the entry's check.  Unit scale: remainder 0, weights (1, 0).
-__device__ __forceinline__ InfTap pyr_tap(int dst, int n_in, int den, FastDiv div) {
+__device__ __forceinline__ Tap pyr_tap(int dst, int n_in, int den, FastDiv div) {
   const int num = dst * (n_in - 1);
   int i0 = fdiv(num, div);
   const int r = num - i0 * den;
   if (i0 > n_in - 1) i0 = n_in - 1;                  // n_out = 1 only: dst = 0, nothing to clamp otherwise
-  InfTap t;
+  Tap t;
   t.i0 = i0;
   t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
   t.w1 = (float)r / (float)den;
@@ -74,11 +58,8 @@ __global__ __launch_bounds__(kInfB) void image_pyramid(const float* __restrict__
   float* om = o + (size_t)planes * n_out;
   for (int p = blockIdx.x * kInfB + threadIdx.x; p < n_out; p += gridDim.x * kInfB) {
     const int oy = fdiv(p, div_ws), ox = p - oy * Ws;
-    const InfTap ty = pyr_tap(oy, H, den_h, div_h), tx = pyr_tap(ox, W, den_w, div_w);
-    const int r0 = ty.i0 * W, r1 = ty.i1 * W;
-    const float top = tx.w0 * pl[r0 + tx.i0] + tx.w1 * pl[r0 + tx.i1];
-    const float bot = tx.w0 * pl[r1 + tx.i0] + tx.w1 * pl[r1 + tx.i1];
-    const float val = ty.w0 * top + ty.w1 * bot;      // unit scale: weights (1, 0), val = the source pixel
+    const TapPix q = tap_pix(pyr_tap(oy, H, den_h, div_h), pyr_tap(ox, W, den_w, div_w), W);
+    const float val = tap_mix(q, pl[q.o00], pl[q.o01], pl[q.o10], pl[q.o11]);   // unit scale: weights (1, 0), the source pixel
     o[p] = val;
     if (with_flip) om[oy * Ws + (Ws - 1 - ox)] = val;
   }
@@ -92,8 +73,38 @@ struct InferSources {                                // by value
   int n;
 };
 
+// The softmax over the classes of source s's bilinear taps at output pixel (oy, ox) of image b, as v[c] * (the value returned):
+// v[0..C) = exp(tap mix - their maximum), returned 1 / their sum.
+template <int CT>
+__device__ __forceinline__ float source_probs(const InferSources& src, int s, int b, int C, int oy, int ox, int W, float (&v)[CT]) {
+  const int h = src.h[s], w = src.w[s], hw = h * w;
+  const float* xb = src.x[s] + (size_t)b * C * hw;
+  const int sx = ((src.flip >> s) & 1u) ? W - 1 - ox : ox;
+  const TapPix q = tap_pix(tap_ac(oy, src.sh[s], h), tap_ac(sx, src.sw[s], w), w);
+  float mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (c < C) {
+      const float* pl = xb + (size_t)c * hw;
+      v[c] = tap_mix(q, pl[q.o00], pl[q.o01], pl[q.o10], pl[q.o11]);
+      mx = fmaxf(mx, v[c]);
+    }
+  float den = 0.f;
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (c < C) {
+      v[c] = expf(v[c] - mx);
+      den += v[c];
+    }
+  return 1.f / den;
+}
+
 // CT = compile-time class count (19), kInfMaxC = the generic runtime-C instantiation; MODE = DASAC_INFER_MEAN / _MAX.
-template <int CT, int MODE>
+// SINGLE (dasac_infer_labels): source 0 alone is the fused result -- no acc[] beside v[], no source loop, no `probs`; the bits
+// are those of the mean over one source (0 + p = p and p * 1 = p exactly).  The fused value is a local of the argmax loop and
+// `probs` is stored from there: written back into acc[] under the runtime-C predicate it costs the generic instantiation a wave
+// per SIMD (143 instead of 124 VGPRs).
+template <int CT, int MODE, bool SINGLE>
 __global__ __launch_bounds__(kInfB) void infer_fuse(const InferSources src, int Crt, int H, int W, FastDiv div_w,
                                                     const uint8_t* __restrict__ lut, uint8_t* __restrict__ labels,
                                                     float* __restrict__ conf, float* __restrict__ probs, int blocks_per_image) {
@@ -102,62 +113,39 @@ __global__ __launch_bounds__(kInfB) void infer_fuse(const InferSources src, int 
   const int HW = H * W;
   for (int p = chunk * kInfB + threadIdx.x; p < HW; p += blocks_per_image * kInfB) {
     const int oy = fdiv(p, div_w), ox = p - oy * W;
-    float acc[CT];                                   // probabilities are >= 0: 0 starts the sum and the maximum alike
+    float acc[CT], scale;                            // the fused value of class c is acc[c] * scale
+    if (SINGLE) {
+      scale = source_probs<CT>(src, 0, b, C, oy, ox, W, acc);
+    } else {
 #pragma unroll
-    for (int c = 0; c < CT; ++c) acc[c] = 0.f;
-    for (int s = 0; s < src.n; ++s) {
-      const int h = src.h[s], w = src.w[s], hw = h * w;
-      const float* xb = src.x[s] + (size_t)b * C * hw;
-      const int sx = ((src.flip >> s) & 1u) ? W - 1 - ox : ox;
-      const InfTap ty = inf_tap(oy, src.sh[s], h), tx = inf_tap(sx, src.sw[s], w);
-      const int o00 = ty.i0 * w + tx.i0, o01 = ty.i0 * w + tx.i1, o10 = ty.i1 * w + tx.i0, o11 = ty.i1 * w + tx.i1;
-      float v[CT];
-      float mx = -INFINITY;
+      for (int c = 0; c < CT; ++c) acc[c] = 0.f;     // probabilities are >= 0: 0 starts the sum and the maximum alike
+      for (int s = 0; s < src.n; ++s) {
+        float v[CT];
+        const float inv = source_probs<CT>(src, s, b, C, oy, ox, W, v);
 #pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        if (c < C) {
-          const float* pl = xb + (size_t)c * hw;
-          const float top = tx.w0 * pl[o00] + tx.w1 * pl[o01];
-          const float bot = tx.w0 * pl[o10] + tx.w1 * pl[o11];
-          v[c] = ty.w0 * top + ty.w1 * bot;
-          mx = fmaxf(mx, v[c]);
-        }
+        for (int c = 0; c < CT; ++c)
+          if (c < C) {
+            const float pr = v[c] * inv;
+            acc[c] = MODE == DASAC_INFER_MEAN ? acc[c] + pr : fmaxf(acc[c], pr);
+          }
       }
-      float den = 0.f;
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (c < C) {
-          v[c] = expf(v[c] - mx);
-          den += v[c];
-        }
-      const float inv = 1.f / den;
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (c < C) {
-          const float pr = v[c] * inv;
-          acc[c] = MODE == DASAC_INFER_MEAN ? acc[c] + pr : fmaxf(acc[c], pr);
-        }
+      scale = 1.f / (float)src.n;                    // one source: exactly 1
     }
-    const float norm = 1.f / (float)src.n;           // one source: exactly 1
+    float* pb = (!SINGLE && probs) ? probs + (size_t)b * C * HW + p : nullptr;
     int best = 0;
     float bp = -1.f;
 #pragma unroll
     for (int c = 0; c < CT; ++c)
       if (c < C) {
-        if (MODE == DASAC_INFER_MEAN) acc[c] *= norm;
-        if (acc[c] > bp) {                           // strict: the first maximum wins
-          bp = acc[c];
+        const float f = (SINGLE || MODE == DASAC_INFER_MEAN) ? acc[c] * scale : acc[c];
+        if (f > bp) {                                // strict: the first maximum wins, as torch.argmax / numpy.argmax
+          bp = f;
           best = c;
         }
+        if (pb) pb[(size_t)c * HW] = f;
       }
     labels[(size_t)b * HW + p] = lut ? lut[best] : (uint8_t)best;
     if (conf) conf[(size_t)b * HW + p] = bp;
-    if (probs) {
-      float* pb = probs + (size_t)b * C * HW + p;
-#pragma unroll
-      for (int c = 0; c < CT; ++c)
-        if (c < C) pb[(size_t)c * HW] = acc[c];
-    }
   }
 }
 
@@ -179,6 +167,41 @@ extern "C" int dasac_image_pyramid(const float* image, int B, int Cin, int H, in
   return DASAC_OK;
 }
 
+// One launch of the label-map kernel; `single`: a.n == 1, unflipped, mean, no probs (dasac_infer_labels).
+static void launch_infer_fuse(const InferSources& a, bool single, int B, int C, int H, int W, int mode, const uint8_t* lut,
+                              uint8_t* labels, float* conf, float* probs, dasac_stream_t stream) {
+  const int per = stream_grid((int64_t)H * W, kInfB, (kNumCu * 16 + B - 1) / B);
+  hipStream_t st = as_stream(stream);
+#define DASAC_FUSE(CT, MODE, SINGLE)                                                                                          \
+  hipLaunchKernelGGL((infer_fuse<CT, MODE, SINGLE>), dim3(per * B), dim3(kInfB), 0, st, a, C, H, W, fast_div(W), lut, labels, \
+                     conf, probs, per)
+  if (single) {
+    if (C == 19) DASAC_FUSE(19, DASAC_INFER_MEAN, true); else DASAC_FUSE(kInfMaxC, DASAC_INFER_MEAN, true);
+  } else if (C == 19) {
+    if (mode == DASAC_INFER_MEAN) DASAC_FUSE(19, DASAC_INFER_MEAN, false); else DASAC_FUSE(19, DASAC_INFER_MAX, false);
+  } else {
+    if (mode == DASAC_INFER_MEAN) DASAC_FUSE(kInfMaxC, DASAC_INFER_MEAN, false); else DASAC_FUSE(kInfMaxC, DASAC_INFER_MAX, false);
+  }
+#undef DASAC_FUSE
+}
+
+extern "C" int dasac_infer_labels(const float* logits, int B, int C, int h, int w, int H, int W, const uint8_t* lut,
+                                  uint8_t* labels, float* conf, dasac_stream_t stream) {
+  DASAC_REQUIRE(logits && labels, "infer_labels: null pointer");
+  DASAC_REQUIRE(B > 0 && C > 0 && C <= kInfMaxC && h > 0 && w > 0 && H > 0 && W > 0, "infer_labels: bad shape");
+  DASAC_REQUIRE((int64_t)H * W < (1ll << 30) && (int64_t)h * w < (1ll << 30), "infer_labels: plane too large");
+  InferSources a = {};
+  a.n = 1;
+  a.x[0] = logits;
+  a.h[0] = h;
+  a.w[0] = w;
+  a.sh[0] = ac_scale(h, H);
+  a.sw[0] = ac_scale(w, W);
+  launch_infer_fuse(a, true, B, C, H, W, DASAC_INFER_MEAN, lut, labels, conf, nullptr, stream);
+  DASAC_CHECK_LAUNCH("infer_labels");
+  return DASAC_OK;
+}
+
 extern "C" int dasac_infer_fuse(const dasac_infer_source* sources, int n_sources, int B, int C, int H, int W, int mode,
                                 const uint8_t* lut, uint8_t* labels, float* conf, float* probs, dasac_stream_t stream) {
   DASAC_REQUIRE(sources && labels, "infer_fuse: null pointer");
@@ -194,20 +217,11 @@ extern "C" int dasac_infer_fuse(const dasac_infer_source* sources, int n_sources
     a.x[s] = q.logits;
     a.h[s] = q.h;
     a.w[s] = q.w;
-    a.sh[s] = inf_scale(q.h, H);
-    a.sw[s] = inf_scale(q.w, W);
+    a.sh[s] = ac_scale(q.h, H);
+    a.sw[s] = ac_scale(q.w, W);
     if (q.flip) a.flip |= 1u << s;
   }
-  const int per = stream_grid((int64_t)H * W, kInfB, (kNumCu * 16 + B - 1) / B);
-  hipStream_t st = as_stream(stream);
-#define DASAC_FUSE(CT, MODE) \
-  hipLaunchKernelGGL((infer_fuse<CT, MODE>), dim3(per * B), dim3(kInfB), 0, st, a, C, H, W, fast_div(W), lut, labels, conf, probs, per)
-  if (C == 19) {
-    if (mode == DASAC_INFER_MEAN) DASAC_FUSE(19, DASAC_INFER_MEAN); else DASAC_FUSE(19, DASAC_INFER_MAX);
-  } else {
-    if (mode == DASAC_INFER_MEAN) DASAC_FUSE(kInfMaxC, DASAC_INFER_MEAN); else DASAC_FUSE(kInfMaxC, DASAC_INFER_MAX);
-  }
-#undef DASAC_FUSE
+  launch_infer_fuse(a, false, B, C, H, W, mode, lut, labels, conf, probs, stream);
   DASAC_CHECK_LAUNCH("infer_fuse");
   return DASAC_OK;
 }

@@ -19,9 +19,8 @@
 // is taken at each of the four taps and every class is resized on its own, as the reference does at full resolution; no
 // full-resolution intermediate exists.  Arg-max: the first maximum wins (strict >), an all-zero pixel gives class 0.
 //
-// Resize weights: ATen's align_corners=True ones (UpSample.h: scale = (in - 1) / (out - 1), 0 for an output extent of 1;
-// i0 = min((int)(scale * dst), in - 1), i1 = i0 + (i0 < in - 1), w1 = scale * dst - i0) -- ac_scale / tap_ac of head.hip restated.
-// Both tap indices are clamped inside the plane whatever the scale is: shrinking, enlarging, extent 1, any H x W.
+// Resize weights: ATen's align_corners=True ones, tap_ac / ac_scale of bilinear.hpp; both tap indices stay inside the plane
+// whatever the scale is: shrinking, enlarging, extent 1, any H x W.
 //
 // Shape: block = 64 lanes along output x by 4 output rows; (job, image) = blockIdx.z, so the job record, the image
 // bases and the row taps are wave-uniform; a lane adds ONE 32-bit element offset per tap to a scalar plane base.  Plain loads and
@@ -30,6 +29,7 @@
 // The strip is float32 [B,3,h,P*w] (the reference's `visuals`); the same thread can also write the u8 rows the reference's
 // `_visualise_grid` makes of it (:264: `.mul(255).clamp(0, 255).byte()`, truncation).  dasac_vis_grid lays float rows out as
 // torchvision's make_grid(nrow=1, padding, pad_value) does (:269).
+#include "bilinear.hpp"
 #include "common.hpp"
 
 namespace dasac {
@@ -41,38 +41,9 @@ struct VisNorm {                                       // by value
   float mean[3], std[3];
 };
 
-struct VisTap {
-  int i0, i1;
-  float w0, w1;
-};
-
-__device__ __forceinline__ VisTap vis_tap(int dst, float scale, int n_in) {
-  const float src = scale * (float)dst;
-  int i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
-  if (i0 < 0) i0 = 0;
-  VisTap t;
-  t.i0 = i0;
-  t.i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  t.w1 = src - (float)i0;
-  t.w0 = 1.f - t.w1;
-  return t;
-}
-
-struct VisPix {                                        // the four taps of one output pixel inside an H x W plane
-  int o00, o01, o10, o11;
-  float wx0, wx1, wy0, wy1;
-};
-
-__device__ __forceinline__ float vis_mix(const VisPix& p, float v00, float v01, float v10, float v11) {
-  const float top = p.wx0 * v00 + p.wx1 * v01;
-  const float bot = p.wx0 * v10 + p.wx1 * v11;
-  return p.wy0 * top + p.wy1 * bot;
-}
-
 // downsize(denorm(img))[ch] at the pixel; `plane` = the channel's H x W plane
-__device__ __forceinline__ float vis_image(const float* __restrict__ plane, const VisPix& p, float mean, float std) {
-  return vis_mix(p, plane[p.o00] * std + mean, plane[p.o01] * std + mean, plane[p.o10] * std + mean, plane[p.o11] * std + mean);
+__device__ __forceinline__ float vis_image(const float* __restrict__ plane, const TapPix& p, float mean, float std) {
+  return tap_mix(p, plane[p.o00] * std + mean, plane[p.o01] * std + mean, plane[p.o10] * std + mean, plane[p.o11] * std + mean);
 }
 
 __device__ __forceinline__ int vis_saturate(int64_t v) { return v < 0 ? 0 : (v > 255 ? 255 : (int)v); }
@@ -107,14 +78,7 @@ __global__ __launch_bounds__(kVisX * kVisY) void vis_panels(const dasac_vis_job*
 
   const int H = job.H, W = job.W, C = job.C;
   const size_t HW = (size_t)H * W;
-  const float sh = h > 1 ? (float)(H - 1) / (float)(h - 1) : 0.f, sw = w > 1 ? (float)(W - 1) / (float)(w - 1) : 0.f;
-  const VisTap ty = vis_tap(y, sh, H), tx = vis_tap(x, sw, W);
-  VisPix p;
-  p.o00 = ty.i0 * W + tx.i0;
-  p.o01 = ty.i0 * W + tx.i1;
-  p.o10 = ty.i1 * W + tx.i0;
-  p.o11 = ty.i1 * W + tx.i1;
-  p.wx0 = tx.w0, p.wx1 = tx.w1, p.wy0 = ty.w0, p.wy1 = ty.w1;
+  const TapPix p = tap_pix(tap_ac(y, ac_scale(H, h), H), tap_ac(x, ac_scale(W, w), W), W);
 
   const size_t plane_out = (size_t)h * P * w;          // one channel of one image of the strip
   const size_t obase = (size_t)b * 3 * plane_out;      // scalar
@@ -142,7 +106,7 @@ __global__ __launch_bounds__(kVisX * kVisY) void vis_panels(const dasac_vis_job*
     const int l10 = vis_saturate(lab[p.o10]) * 3, l11 = vis_saturate(lab[p.o11]) * 3;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-      const float rgb = vis_mix(p, (float)palette[l00 + ch] / 255.f, (float)palette[l01 + ch] / 255.f,
+      const float rgb = tap_mix(p, (float)palette[l00 + ch] / 255.f, (float)palette[l01 + ch] / 255.f,
                                 (float)palette[l10 + ch] / 255.f, (float)palette[l11 + ch] / 255.f);
       vis_store(strip, rows, obase + ch * plane_out, ooff, back[ch] + 0.7f * rgb);
     }
@@ -184,7 +148,7 @@ __global__ __launch_bounds__(kVisX * kVisY) void vis_panels(const dasac_vis_job*
         v10 = expf(v10 - m10) / r10;
         v11 = expf(v11 - m11) / r11;
       }
-      const float v = vis_mix(p, v00, v01, v10, v11);
+      const float v = tap_mix(p, v00, v01, v10, v11);
       if (v > bp) {                                    // strict: the first maximum wins, as Tensor.max(1)
         bp = v;
         best = c;
@@ -197,7 +161,7 @@ __global__ __launch_bounds__(kVisX * kVisY) void vis_panels(const dasac_vis_job*
       vis_store(strip, rows, obase + ch * plane_out, ooff, back[ch] + 0.7f * ((float)palette[l + ch] / 255.f));
   } else {                                             // DASAC_VIS_CONF: one plane per image
     const float* pl = reinterpret_cast<const float*>(job.src) + (size_t)b * HW;
-    conf = vis_mix(p, pl[p.o00], pl[p.o01], pl[p.o10], pl[p.o11]);
+    conf = tap_mix(p, pl[p.o00], pl[p.o01], pl[p.o10], pl[p.o11]);
   }
   const int k = vis_cmap_index(1.f - conf) * 3;
   const unsigned o = job.kind == DASAC_VIS_SCORES ? ooff2 : ooff;

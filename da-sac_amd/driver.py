@@ -369,17 +369,24 @@ def load_checkpoint(path, net, optim=None, map_location="cpu"):
 CITYSCAPES_TRAIN_TO_ID = (7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33)
 
 
-def infer_label_maps(net, image, lut=None, teacher=False, want_conf=False):
-    """infer_val.py:160-163 + the writer's argmax / id mapping, without materialising logits_up or the softmax:
-    backbone -> low-resolution logits -> ONE kernel -> uint8 label map [B,H,W] on the device (PNG writing stays on
-    the host).  `lut`: uint8 tensor / sequence (e.g. CITYSCAPES_TRAIN_TO_ID) or None for train ids."""
-    from dasac_hip import ops
+def _infer_backbone_and_lut(net, image, lut, teacher):
+    """What both inference paths start from: the network that gives the logits (the unwrapped net itself, or SAC's student
+    backbone / `slow_net` teacher) and `lut` as a uint8 tensor on the image's device (or None)."""
     core = net.module if hasattr(net, "module") else net
     backbone = core
     if hasattr(core, "backbone"):
         backbone = core.slow_net if teacher else core.backbone
     if lut is not None and not torch.is_tensor(lut):
         lut = torch.tensor(list(lut), dtype=torch.uint8, device=image.device)
+    return backbone, lut
+
+
+def infer_label_maps(net, image, lut=None, teacher=False, want_conf=False):
+    """infer_val.py:160-163 + the writer's argmax / id mapping, without materialising logits_up or the softmax:
+    backbone -> low-resolution logits -> ONE kernel -> uint8 label map [B,H,W] on the device (PNG writing stays on
+    the host).  `lut`: uint8 tensor / sequence (e.g. CITYSCAPES_TRAIN_TO_ID) or None for train ids."""
+    from dasac_hip import ops
+    backbone, lut = _infer_backbone_and_lut(net, image, lut, teacher)
     with torch.no_grad():
         logits = backbone._logits(image)
         return ops.infer_labels(logits, image.shape[-2:], lut, want_conf)
@@ -424,12 +431,7 @@ def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="me
     from dasac_hip import ops
     B, _, H, W = image.shape
     plan = _ms_plan(H, W, scales, flip)
-    core = net.module if hasattr(net, "module") else net
-    backbone = core
-    if hasattr(core, "backbone"):
-        backbone = core.slow_net if teacher else core.backbone
-    if lut is not None and not torch.is_tensor(lut):
-        lut = torch.tensor(list(lut), dtype=torch.uint8, device=image.device)
+    backbone, lut = _infer_backbone_and_lut(net, image, lut, teacher)
     sources, flips = [], []
     with torch.no_grad():
         for Hs, Ws, resample in plan:

@@ -258,8 +258,8 @@ int dasac_infer_labels(const float* logits, int B, int C, int h, int w, int H, i
  *     fused = (p_0 + p_1 + ...) * (1.f / n) in source order (DASAC_INFER_MEAN) or max_s p_s (DASAC_INFER_MAX);
  *     labels u8 [B,H,W] = lut[argmax_c fused] (first maximum wins; lut NULL: the class index), conf f32 [B,H,W] (optional) = the
  *     winning fused value, probs f32 [B,C,H,W] (optional) = all of them (what infer_val.py's D_SAVE_RAW stores).
- *     `sources` is a HOST array; its records travel to the kernel by value: no device table, no workspace.  One unflipped
- *     source gives dasac_infer_labels' bits.  C <= 32.  1 (+4) (+4C) bytes written per output pixel. */
+ *     `sources` is a HOST array; its records travel to the kernel by value: no device table, no workspace.  Both entries run
+ *     the same kernel: dasac_infer_labels is one unflipped source.  C <= 32.  1 (+4) (+4C) bytes written per output pixel. */
 #define DASAC_INFER_MAX_SOURCES 8
 #define DASAC_INFER_MEAN 0
 #define DASAC_INFER_MAX 1

@@ -10,6 +10,7 @@ import ctypes
 import functools
 from types import SimpleNamespace as NS
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
@@ -21,6 +22,10 @@ pytestmark = pytest.mark.gpu
 
 CASE1 = dict(B=2, C=19, size=(61, 83), shapes=[(9, 12), (17, 23), (5, 7), (9, 12), (61, 83)], flips=[0, 1, 0, 1, 0])
 CASE2 = dict(B=1, C=5, size=(33, 29), shapes=[(1, 3), (9, 7), (4, 1)], flips=[1, 0, 1])
+# (case, source) of _logits() whose single-source label map is pinned by tests/golden/g21_infer_labels_bits.npz: 19 classes (the
+# compile-time instantiation) at 17 x 23 -> 61 x 83 and at unit scale (weights (1, 0)); 5 classes (runtime C) from one row and
+# from one column (degenerate taps).  make_goldens_infer_bits.py stores entry i as labels_i / conf_i.
+BITS_INPUTS = ((0, 1), (0, 4), (1, 0), (1, 2))
 
 
 @functools.lru_cache(maxsize=None)
@@ -93,14 +98,27 @@ def test_infer_fuse_generic_class_count_and_degenerate_taps(mode):
     _check_against_float64(1, mode)
 
 
-def test_infer_fuse_exact_identities():
+def test_infer_fuse_exact_identities(golden):
+    """dasac_infer_labels and dasac_infer_fuse over one unflipped source run the same kernel, so comparing them with each other
+    says nothing: both are held to the stored bits of the separate infer_labels<CT> kernel that preceded it (g21, labels and
+    confidence), and the winner among `probs` to the confidence."""
     from dasac_hip import ops, DasacError
     from dasac_hip import lib as L
+    g21 = golden("g21_infer_labels_bits")
+    bits = lambda t: t.cpu().numpy().view(np.uint32)
+    for i, (case_index, source) in enumerate(BITS_INPUTS):
+        x, size = _logits()[case_index][source].cuda(), (CASE1, CASE2)[case_index]["size"]
+        assert tuple(x.shape) == tuple(g21["shape_%d" % i])
+        lab1, conf1 = ops.infer_labels(x, size, want_conf=True)
+        lab, conf, probs = ops.infer_fuse([x], [0], size, "mean", want_conf=True, want_probs=True)
+        for got_lab, got_conf in ((lab1, conf1), (lab, conf)):
+            assert np.array_equal(got_lab.cpu().numpy(), g21["labels_%d" % i])
+            assert np.array_equal(bits(got_conf), g21["conf_%d" % i].view(np.uint32))
+        assert np.array_equal(bits(probs.gather(1, lab.long()[:, None])[:, 0]), bits(conf))
+        assert np.array_equal(bits(probs.max(1).values), bits(conf))
     x = _logits()[0][1].cuda()                       # [2,19,17,23]
     size = CASE1["size"]
-    lab1, conf1 = ops.infer_labels(x, size, want_conf=True)
     lab, conf, probs = ops.infer_fuse([x], [0], size, "mean", want_conf=True, want_probs=True)
-    assert torch.equal(lab, lab1) and torch.equal(conf, conf1)
     labf, conff, probsf = ops.infer_fuse([x], [1], size, "mean", want_conf=True, want_probs=True)
     assert torch.equal(labf, lab.flip(-1)) and torch.equal(conff, conf.flip(-1)) and torch.equal(probsf, probs.flip(-1))
     one = ops.infer_fuse([x], [0], size, "max", want_conf=True, want_probs=True)
