@@ -882,13 +882,17 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad(const float* __restric
       qow = prr - qoh * g.OW;
     }
     const int tap_off = QTAP ? e0.x - e0.w : 0;            // dh*W + dw
+    const unsigned x_elems = g.x_bytes >> 2;
     // x offset of (image, k tile's first channel + prow4, quad start + tap), in elements.  The k tile's first channel rides in the
     // per-lane part so that it is negative only in the first rows of image 0, channel 0 (those quads take the per-element path:
     // a wrapped unsigned offset fails the range check whatever the scalar offset adds)
 #define DASAC_WGQ_LOAD()                                                                             \
   {                                                                                                  \
     const int xo = pn * g.CxHW + (QTAP ? e0.w : 0) + prr + tap_off + prow4 * planeHW;                \
-    const bool whole = (pix + 3 < p_end) & (prr + 3 < OHW) & (!QTAP || xo >= 0);                     \
+    /* (the channel step of the loads below rides in the scalar offset, which the hardware's range check leaves out: a tap  \
+       quad of the last image's last channels must not run past the end of x -- the per-element path poisons those lanes) */ \
+    const bool whole = (pix + 3 < p_end) & (prr + 3 < OHW) &                                         \
+                       (!QTAP || (xo >= 0 && (unsigned)(xo + 3 + (BQ - 1) * 32 * planeHW) < x_elems)); \
     if (__builtin_amdgcn_ballot_w64(!whole) == 0) {                                                  \
       const unsigned vz = (unsigned)(pn * zimg_q + prr + prow4 * OHW) * 4u;                          \
       const unsigned vx = (unsigned)xo * 4u;                                                         \

@@ -1,0 +1,233 @@
+// Winograd F(2x2,3x3) for the wide dilated 3x3 convolutions (layer4 of the ResNet-101 backbone: 512 -> 512, dilation 4, 97x97
+// maps; models/deeplabv2.py:65-66), UNFUSED: three streaming kernels around sixteen calls of the existing dasac_conv_gemm.
+//
+//   filter transform   U[pt] = G g G^T per (cout, cin), frozen-BN scale folded in, written as the packed operand of a 1x1 conv
+//   input transform    V[pt][c][tile] = (B^T d B)[pt] of the 4x4 patch (stride = dilation) of every tile
+//   16 point GEMMs     Y[pt][m][tile] = sum_c U[pt][m][c] * V[pt][c][tile]          (dasac_conv_gemm, 1x1, H = 1, W = tiles)
+//   output transform   out[n][m][y][x] = epi((A^T Y A)[ey][ex]) -- shift, ReLU, ReLU bits recorded or consumed
+//
+// 2.25 x fewer multiplies than the direct contraction; the price is two passes over [16][C][tiles] tensors.  No new matrix kernel.
+// Index arithmetic lives in winograd_index.hpp and is walked on the host by tools/winograd_index_check.cpp.  Every global access
+// goes through a buffer descriptor of the tensor's exact extent with the whole offset in the per-lane operand (the scalar
+// offset is not range checked by the hardware): an offset past the extent reads zero / stores nothing.
+#include "common.hpp"
+#include "winograd_index.hpp"
+
+namespace dasac {
+namespace wino {
+
+constexpr int kRsrcFlags = 0x00020000;   // raw buffer, 32-bit data format (as conv_igemm.hip)
+constexpr int kBlock = 256;
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, kRsrcFlags);
+}
+__device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t r, unsigned voff) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
+}
+__device__ __forceinline__ void st(__amdgpu_buffer_rsrc_t r, unsigned voff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, 0);
+}
+
+// ---- filter transform ------------------------------------------------------------------------------------------------------
+// One thread per element (k, m) of the packed [Kpad/4][Mpad][4] matrix; it writes all 16 points (K and M padding as zeros).
+// mode 0 (forward): m = cout, k = cin, g = w[m][k] * scale[m].   mode 1 (data gradient): m = cin, k = cout,
+// g = rot180(w[k][m]) * scale[k].   U = G g G^T with G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]].
+__global__ __launch_bounds__(kBlock) void filter_transform(const float* __restrict__ Wt, const float* __restrict__ scale,
+                                                            float* __restrict__ U, int Cout, int Cin, int Mpad, int Kpad, int mode,
+                                                            unsigned w_bytes, unsigned u_bytes) {
+  const int idx = blockIdx.x * kBlock + threadIdx.x;      // == offset inside one point's packed matrix
+  const int per_point = Kpad * Mpad;
+  if (idx >= per_point) return;
+  const __amdgpu_buffer_rsrc_t rw = make_rsrc(Wt, w_bytes), ru = make_rsrc(U, u_bytes);
+  const int row4 = Mpad * 4;
+  const int kq = idx / row4, rem = idx - kq * row4;
+  const int m = rem >> 2, k = kq * 4 + (rem & 3);
+  const int M = mode == 0 ? Cout : Cin, K = mode == 0 ? Cin : Cout;
+  float g[3][3];
+  const bool real = m < M && k < K;
+  const int co = mode == 0 ? m : k, ci = mode == 0 ? k : m;
+  const float s = (real && scale) ? ld(make_rsrc(scale, (unsigned)Cout * 4u), (unsigned)co * 4u) : 1.f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const int tap = mode == 0 ? a * 3 + b : (2 - a) * 3 + (2 - b);
+      const unsigned off = real ? (unsigned)((co * Cin + ci) * 9 + tap) * 4u : kOutside;
+      g[a][b] = ld(rw, off) * s;
+    }
+  float t[4][3];                                           // G g
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    t[0][b] = g[0][b];
+    t[1][b] = 0.5f * ((g[0][b] + g[2][b]) + g[1][b]);
+    t[2][b] = 0.5f * ((g[0][b] + g[2][b]) - g[1][b]);
+    t[3][b] = g[2][b];
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const float u[4] = {t[a][0], 0.5f * ((t[a][0] + t[a][2]) + t[a][1]), 0.5f * ((t[a][0] + t[a][2]) - t[a][1]), t[a][2]};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) st(ru, (unsigned)((a * 4 + b) * per_point + idx) * 4u, u[b]);
+  }
+}
+
+// ---- input transform -------------------------------------------------------------------------------------------------------
+// grid (ceil(T / 256), C): one thread per (channel, tile), lanes along tiles.  V = B^T d B, B^T = [[1,0,-1,0],[0,1,1,0],[0,-1,1,0],[0,1,0,-1]].
+__global__ __launch_bounds__(kBlock) void input_transform(const float* __restrict__ X, float* __restrict__ V, Geom g, int C,
+                                                           unsigned x_bytes, unsigned v_bytes) {
+  const int tile = blockIdx.x * kBlock + threadIdx.x;
+  if (tile >= g.T) return;
+  const int c = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(X, x_bytes), rv = make_rsrc(V, v_bytes);
+  int n, y0, x0;
+  tile_origin(g, tile, n, y0, x0);
+  float d[4][4];
+#pragma unroll
+  for (int ky = 0; ky < 4; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < 4; ++kx) d[ky][kx] = ld(rx, patch_offset(g, C, n, c, y0, x0, ky, kx));
+  float t[4][4];                                           // B^T d
+#pragma unroll
+  for (int kx = 0; kx < 4; ++kx) {
+    t[0][kx] = d[0][kx] - d[2][kx];
+    t[1][kx] = d[1][kx] + d[2][kx];
+    t[2][kx] = d[2][kx] - d[1][kx];
+    t[3][kx] = d[1][kx] - d[3][kx];
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const float v[4] = {t[a][0] - t[a][2], t[a][1] + t[a][2], t[a][2] - t[a][1], t[a][1] - t[a][3]};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) st(rv, point_offset(g, C, a * 4 + b, c, tile), v[b]);
+  }
+}
+
+// ---- output transform ------------------------------------------------------------------------------------------------------
+// grid (ceil(N*H*W / 256), M): one thread per OUTPUT element, lanes along the flattened (n, y, x) pixel index -- the pixel axis of
+// the ReLU bit masks (conv_igemm.hip Epilogue: bits[m][pix >> 5] bit pix & 31), so a wave ballot is two mask words, as in the
+// direct epilogue.  Output (ey, ex) of a tile is sum_j sum_k sy_j sx_k Y[ey + j][ex + k], signs (+,+,+) for e = 0 and (+,-,-)
+// for e = 1 (A^T = [[1,1,1,0],[0,1,-1,-1]]): nine loads; the four outputs of a tile re-read its values from cache.
+// BITS: 0 none, 1 record (v > 0 after the ReLU), 2 mask (v = bit ? v : 0).
+template <int BITS>
+__global__ __launch_bounds__(kBlock) void output_transform(const float* __restrict__ Y, float* __restrict__ Out, Geom g, int M,
+                                                            const float* __restrict__ shift, int relu,
+                                                            const unsigned* __restrict__ mbits, unsigned* __restrict__ obits,
+                                                            int w32, unsigned y_bytes, unsigned out_bytes, unsigned bits_bytes) {
+  const int pix = blockIdx.x * kBlock + threadIdx.x;
+  const int m = blockIdx.y;
+  const bool live = pix < g.N * g.HW;
+  const __amdgpu_buffer_rsrc_t ry = make_rsrc(Y, y_bytes), ro = make_rsrc(Out, out_bytes);
+  int n = 0, rem = 0, tile = 0, ey = 0, ex = 0;
+  if (live) pixel_tile(g, pix, n, rem, tile, ey, ex);
+  float v[3][3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[j][k] = ld(ry, live ? point_offset(g, M, (ey + j) * 4 + ex + k, m, tile) : kOutside);
+  const float sy = ey ? -1.f : 1.f, sx = ex ? -1.f : 1.f;
+  float row[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) row[j] = (v[j][0] + sx * v[j][1]) + sx * v[j][2];
+  float o = (row[0] + sy * row[1]) + sy * row[2];
+  if (shift) o = o + ld(make_rsrc(shift, (unsigned)M * 4u), (unsigned)m * 4u);
+  if (relu) o = fmaxf(o, 0.f);
+  if constexpr (BITS == 2) {
+    const __amdgpu_buffer_rsrc_t rb = make_rsrc(mbits, bits_bytes);
+    const unsigned word = __builtin_amdgcn_raw_buffer_load_b32(rb, live ? (unsigned)(m * w32 + (pix >> 5)) * 4u : kOutside, 0, 0);
+    o = (word >> (pix & 31)) & 1u ? o : 0.f;
+  }
+  st(ro, live ? out_offset(g, M, n, m, rem) : kOutside, o);
+  if constexpr (BITS == 1) {
+    const unsigned long long ballot = __builtin_amdgcn_ballot_w64(live && o > 0.f);
+    const int lane = threadIdx.x & 63;
+    const __amdgpu_buffer_rsrc_t rb = make_rsrc(obits, bits_bytes);
+    // lanes 0 and 32 store the wave's two words; a word whose 32 pixels all lie past the last pixel does not exist
+    const int wcol = pix >> 5;
+    if ((lane & 31) == 0 && wcol < w32)
+      __builtin_amdgcn_raw_buffer_store_b32((unsigned)(lane ? ballot >> 32 : ballot), rb, (unsigned)(m * w32 + wcol) * 4u, 0, 0);
+  }
+}
+
+}  // namespace wino
+}  // namespace dasac
+
+using namespace dasac;
+using dasac::wino::Geom;
+
+static int wino_geom(Geom& g, const char* who, int Nb, int C, int M, int H, int W, int dilation) {
+  DASAC_REQUIRE(Nb > 0 && C > 0 && M > 0 && H > 0 && W > 0 && dilation > 0, "%s: bad geometry", who);
+  DASAC_REQUIRE((int64_t)Nb * H * W < (1ll << 30), "%s: more than 2^30 pixels", who);
+  g = wino::make_geom(Nb, H, W, dilation);
+  const int64_t cmax = C > M ? C : M;
+  DASAC_REQUIRE(16 * cmax * (int64_t)g.T * 4 <= wino::kMaxBytes && cmax * (int64_t)Nb * H * W * 4 <= wino::kMaxBytes,
+                "%s: a tensor exceeds the 4 GiB buffer-descriptor window", who);
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd_tiles(int Nb, int H, int W, int dilation) {
+  if (Nb <= 0 || H <= 0 || W <= 0 || dilation <= 0) return 0;
+  const int64_t t = (int64_t)Nb * wino::make_axis(H, dilation).tiles * wino::make_axis(W, dilation).tiles;
+  return t < (1ll << 30) ? (int)t : 0;
+}
+
+extern "C" int dasac_winograd_filter(const float* w, const float* scale, int Cout, int Cin, int transposed, float* u,
+                                     dasac_stream_t stream) {
+  DASAC_REQUIRE(w && u, "winograd_filter: null pointer");
+  DASAC_REQUIRE(Cout > 0 && Cin > 0, "winograd_filter: bad channel counts");
+  const int M = transposed ? Cin : Cout, K = transposed ? Cout : Cin;
+  const int Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K);
+  const int64_t per_point = (int64_t)Kpad * Mpad;
+  DASAC_REQUIRE(16 * per_point * 4 <= wino::kMaxBytes && (int64_t)Cout * Cin * 9 * 4 <= wino::kMaxBytes,
+                "winograd_filter: operand exceeds the 4 GiB buffer-descriptor window");
+  hipLaunchKernelGGL(wino::filter_transform, dim3((unsigned)((per_point + wino::kBlock - 1) / wino::kBlock)), dim3(wino::kBlock), 0,
+                     as_stream(stream), w, scale, u, Cout, Cin, Mpad, Kpad, transposed ? 1 : 0, (unsigned)((int64_t)Cout * Cin * 9 * 4),
+                     (unsigned)(16 * per_point * 4));
+  DASAC_CHECK_LAUNCH("winograd filter_transform");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd_input(const float* x, int Nb, int C, int H, int W, int dilation, float* v, size_t v_bytes,
+                                    dasac_stream_t stream) {
+  DASAC_REQUIRE(x && v, "winograd_input: null pointer");
+  Geom g;
+  const int rc = wino_geom(g, "winograd_input", Nb, C, C, H, W, dilation);
+  if (rc) return rc;
+  DASAC_REQUIRE(C <= 65535, "winograd_input: more than 65535 channels");
+  const size_t need = (size_t)16 * C * g.T * 4;
+  if (v_bytes < need) return fail(DASAC_EWORKSPACE, "winograd_input: workspace too small (%zu < %zu)", v_bytes, need);
+  hipLaunchKernelGGL(wino::input_transform, dim3((g.T + wino::kBlock - 1) / wino::kBlock, C), dim3(wino::kBlock), 0, as_stream(stream), x,
+                     v, g, C, (unsigned)((int64_t)Nb * C * H * W * 4), (unsigned)need);
+  DASAC_CHECK_LAUNCH("winograd input_transform");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd_output(const float* y, size_t y_bytes, int Nb, int M, int H, int W, int dilation, const float* shift,
+                                     int relu, const uint32_t* mask_bits, uint32_t* relu_bits_out, float* out,
+                                     dasac_stream_t stream) {
+  DASAC_REQUIRE(y && out, "winograd_output: null pointer");
+  DASAC_REQUIRE(!(mask_bits && relu_bits_out), "winograd_output: record the ReLU pattern OR mask with one");
+  DASAC_REQUIRE(!relu_bits_out || relu, "winograd_output: relu_bits_out records the pattern of a ReLU epilogue");
+  Geom g;
+  const int rc = wino_geom(g, "winograd_output", Nb, M, M, H, W, dilation);
+  if (rc) return rc;
+  DASAC_REQUIRE(M <= 65535, "winograd_output: more than 65535 channels");
+  const size_t need = (size_t)16 * M * g.T * 4;
+  if (y_bytes < need) return fail(DASAC_EWORKSPACE, "winograd_output: workspace too small (%zu < %zu)", y_bytes, need);
+  const int npix = Nb * H * W, w32 = (npix + 31) / 32;
+  DASAC_REQUIRE((int64_t)M * w32 * 4 < (1ll << 31), "winograd_output: bit mask exceeds 2 GiB");
+  const unsigned bits_bytes = (unsigned)((int64_t)M * w32 * 4), out_bytes = (unsigned)((int64_t)Nb * M * H * W * 4);
+  const dim3 grid((npix + wino::kBlock - 1) / wino::kBlock, M), block(wino::kBlock);
+  hipStream_t s = as_stream(stream);
+  if (relu_bits_out)
+    hipLaunchKernelGGL(wino::output_transform<1>, grid, block, 0, s, y, out, g, M, shift, relu, mask_bits, relu_bits_out, w32,
+                       (unsigned)need, out_bytes, bits_bytes);
+  else if (mask_bits)
+    hipLaunchKernelGGL(wino::output_transform<2>, grid, block, 0, s, y, out, g, M, shift, relu, mask_bits, relu_bits_out, w32,
+                       (unsigned)need, out_bytes, bits_bytes);
+  else
+    hipLaunchKernelGGL(wino::output_transform<0>, grid, block, 0, s, y, out, g, M, shift, relu, mask_bits, relu_bits_out, w32,
+                       (unsigned)need, out_bytes, bits_bytes);
+  DASAC_CHECK_LAUNCH("winograd output_transform");
+  return DASAC_OK;
+}

@@ -1,0 +1,148 @@
+// Index arithmetic of the Winograd F(2x2,3x3) path for dilated 3x3 convolutions (winograd.hip): phase sizes, the numbering of
+// tiles, patch and tensor offsets.  Plain integer functions, compiled for the host AND the device: the kernels call exactly what
+// the stand-alone host check (tools/winograd_index_check.cpp) walks, so an offset the check has seen in range is the offset the
+// kernel forms.
+//
+// A 3x3 convolution of dilation d, padding d, stride 1 splits into d*d independent undilated 3x3 convolutions ("phases"): output
+// (y, x) with y % d == py, x % d == px only reads input pixels of the same residues.  Along one axis of extent n = q*d + r, phase
+// p holds q + 1 samples for p < r and q otherwise; its samples are cut into F(2,3) tiles of two outputs, t = 0 .. ceil(samples/2)-1.
+// Tile (p, t) produces the outputs o0 = p + 2*d*t and o0 + d (the second one may lie past the map) from the four inputs
+// o0 - d, o0, o0 + d, o0 + 2d (any of them may lie outside: zero padding).
+//
+// Tiles of an axis are numbered g = t*d + p while every phase still has a tile t ("full" part), then the r leftover tiles t = b of
+// the longer phases.  Consecutive g therefore means consecutive pixels: a wave whose lanes run along g reads and writes runs of d
+// adjacent floats, and the four taps of a patch row fill each other's gaps.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define DASAC_HD __host__ __device__ __forceinline__
+#else
+#define DASAC_HD inline
+#endif
+
+namespace dasac {
+namespace wino {
+
+// n / d for 0 <= n < 2^31 by multiply and shift (the scheme of dasac::fast_div in common.hpp, usable on both sides)
+struct Div {
+  unsigned mul, shift;
+  int d;
+};
+DASAC_HD Div make_div(int d) {
+  Div f{0u, 0u, d < 1 ? 1 : d};
+  if (d <= 1) return f;
+  int l = 1;
+  while ((1ll << l) < d) ++l;
+  const unsigned long long p = 1ull << (31 + l);
+  f.mul = (unsigned)((p + (unsigned)d - 1) / (unsigned)d);
+  f.shift = (unsigned)(l - 1);
+  return f;
+}
+DASAC_HD int div(int n, Div f) {
+  return f.mul ? (int)((unsigned)(((unsigned long long)(unsigned)n * f.mul) >> 32) >> f.shift) : n;
+}
+
+struct Axis {
+  int n, d;      // extent, dilation
+  int q, r;      // n = q*d + r
+  int b;         // tiles of a phase with q samples: ceil(q / 2)
+  int full;      // tiles numbered t*d + p (t < b); 0 when q == 0
+  int tiles;     // full + the leftover tiles (t == b) of the r longer phases, which exist when q is even
+  Div by_d;
+};
+DASAC_HD Axis make_axis(int n, int d) {
+  Axis a;
+  a.n = n;
+  a.d = d;
+  a.q = n / d;
+  a.r = n - a.q * d;
+  a.b = (a.q + 1) / 2;
+  a.full = a.b * d;
+  a.tiles = a.full + ((a.q & 1) == 0 ? a.r : 0);
+  a.by_d = make_div(d);
+  return a;
+}
+DASAC_HD int phase_samples(const Axis& a, int p) { return a.q + (p < a.r ? 1 : 0); }
+// tile number -> (phase, tile of the phase)
+DASAC_HD void tile_decode(const Axis& a, int g, int& p, int& t) {
+  if (g < a.full) {
+    t = div(g, a.by_d);
+    p = g - t * a.d;
+  } else {
+    t = a.b;
+    p = g - a.full;
+  }
+}
+DASAC_HD int tile_encode(const Axis& a, int p, int t) { return t < a.b ? t * a.d + p : a.full + p; }
+// first output coordinate of a tile; the patch's inputs are first_out + (k - 1)*d, k = 0..3, its outputs first_out + e*d, e = 0..1
+DASAC_HD int first_out(const Axis& a, int p, int t) { return p + 2 * a.d * t; }
+// output coordinate -> (tile number, e = which of the tile's two outputs)
+DASAC_HD void coord_to_tile(const Axis& a, int o, int& g, int& e) {
+  const int i = div(o, a.by_d), p = o - i * a.d;
+  e = i & 1;
+  g = tile_encode(a, p, i >> 1);
+}
+
+struct Geom {
+  Axis ay, ax;
+  int N, H, W, HW;
+  int tiles_img;          // ay.tiles * ax.tiles
+  int T;                  // N * tiles_img: the pixel axis of the 16 point GEMMs
+  Div by_tiles_img, by_tx, by_hw, by_w;
+};
+DASAC_HD Geom make_geom(int N, int H, int W, int d) {
+  Geom g;
+  g.ay = make_axis(H, d);
+  g.ax = make_axis(W, d);
+  g.N = N;
+  g.H = H;
+  g.W = W;
+  g.HW = H * W;
+  g.tiles_img = g.ay.tiles * g.ax.tiles;
+  g.T = N * g.tiles_img;
+  g.by_tiles_img = make_div(g.tiles_img);
+  g.by_tx = make_div(g.ax.tiles);
+  g.by_hw = make_div(g.HW);
+  g.by_w = make_div(W);
+  return g;
+}
+// tile -> (image, first output row, first output column)
+DASAC_HD void tile_origin(const Geom& g, int tile, int& n, int& y0, int& x0) {
+  n = div(tile, g.by_tiles_img);
+  const int rem = tile - n * g.tiles_img;
+  const int gy = div(rem, g.by_tx), gx = rem - gy * g.ax.tiles;
+  int p, t;
+  tile_decode(g.ay, gy, p, t);
+  y0 = first_out(g.ay, p, t);
+  tile_decode(g.ax, gx, p, t);
+  x0 = first_out(g.ax, p, t);
+}
+// flattened output pixel (n, y, x) -> its tile and position (ey, ex) inside the tile's 2x2 outputs; `rem` = y*W + x
+DASAC_HD void pixel_tile(const Geom& g, int pix, int& n, int& rem, int& tile, int& ey, int& ex) {
+  n = div(pix, g.by_hw);
+  rem = pix - n * g.HW;
+  const int y = div(rem, g.by_w), x = rem - y * g.W;
+  int gy, gx;
+  coord_to_tile(g.ay, y, gy, ey);
+  coord_to_tile(g.ax, x, gx, ex);
+  tile = (n * g.ay.tiles + gy) * g.ax.tiles + gx;
+}
+
+constexpr unsigned kOutside = 0xFFFFFFFFu;   // byte offset of a tap outside the image: past any buffer extent, reads as zero
+
+// byte offset into x [N, C, H, W] of tap (ky, kx) of the patch whose first output is (y0, x0); kOutside for the zero padding
+DASAC_HD unsigned patch_offset(const Geom& g, int C, int n, int c, int y0, int x0, int ky, int kx) {
+  const int y = y0 + (ky - 1) * g.ay.d, x = x0 + (kx - 1) * g.ax.d;
+  if ((unsigned)y >= (unsigned)g.H || (unsigned)x >= (unsigned)g.W) return kOutside;
+  return (unsigned)((n * C + c) * g.HW + y * g.W + x) * 4u;
+}
+// byte offset into a transformed tensor [16][C][T] (V, or the point GEMMs' output)
+DASAC_HD unsigned point_offset(const Geom& g, int C, int pt, int c, int tile) { return (unsigned)((pt * C + c) * g.T + tile) * 4u; }
+// byte offset into an NCHW activation of M channels
+DASAC_HD unsigned out_offset(const Geom& g, int M, int n, int m, int rem) { return (unsigned)((n * M + m) * g.HW + rem) * 4u; }
+// largest tensor the 32-bit byte offsets reach (the limit of conv_igemm.hip)
+constexpr int64_t kMaxBytes = (1ll << 32) - 4096;
+
+}  // namespace wino
+}  // namespace dasac

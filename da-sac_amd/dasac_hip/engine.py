@@ -106,6 +106,10 @@ class ConvOp:
         if keep and self.relu and eng._bits_wanted[self.dst] and ops.bits_ok(spec.cout, spec.cin):
             bits = ops.ReluBits(Nb, spec.cout, OH, OW, xin.device)
             saved["bits"][self.dst] = bits
+        if res is None and ops.winograd_routed(spec, False, Nb, H, W):
+            # wide dilated 3x3 (layer4 conv2): F(2x2,3x3) around sixteen 1x1 GEMMs, 2.25 x fewer multiplies
+            return ops.winograd_conv(xin, eng.winograd_filter(self, False, scale), out, spec.branches[0][2], shift, self.relu,
+                                     bits_out=bits)
         return ops.conv_gemm(xin, eng.packed(self, False, scale), eng.table(self, H, W, False, xin.device), out, (OH, OW),
                              spec.stride, spec.cout, spec.K, 1, shift, res, None, self.relu, bits_out=bits)
 
@@ -130,9 +134,15 @@ class ConvOp:
             else:
                 mask = (bp.relu_pattern(self.src, spec.cin, spec.cout) if spec.stride == 1 else bp.acts[self.src]) if relu else None
                 OH, OW = dz.shape[2:]
-                bp.g[self.src] = ops.conv_dgrad(spec, dz, None, (H, W), scale=scale, res=bp.g.get(self.src), mask=mask,
-                                                table=eng.table(self, OH, OW, True, dz.device),
-                                                packed=eng.packed(self, True, scale))
+                if bp.g.get(self.src) is None and (mask is None or isinstance(mask, ops.ReluBits)) \
+                        and ops.winograd_routed(spec, True, dz.shape[0], OH, OW):
+                    dx = torch.empty((dz.shape[0], spec.cin, H, W), dtype=torch.float32, device=dz.device)
+                    bp.g[self.src] = ops.winograd_conv(dz, eng.winograd_filter(self, True, scale), dx, spec.branches[0][2],
+                                                       mask_bits=mask)
+                else:
+                    bp.g[self.src] = ops.conv_dgrad(spec, dz, None, (H, W), scale=scale, res=bp.g.get(self.src), mask=mask,
+                                                    table=eng.table(self, OH, OW, True, dz.device),
+                                                    packed=eng.packed(self, True, scale))
         if self.res is not None:
             bp.join(self.res, dy_out)
         if bp.sink is not None:
@@ -505,6 +515,16 @@ class Engine:
         if op.expanded is not None:
             return op.expanded.pack(weights, transposed, out=old)
         return ops.conv_pack(op.spec, weights, transposed, scale, out=old, order=ops.gemm_order(op.spec, transposed))
+
+    def winograd_filter(self, op, transposed, scale=None):
+        """Transformed filter (16 packed point matrices) of a conv routed to the Winograd path: cached like `packed`, on the
+        same key -- rebuilt when the weights or the folded scale change, so a teacher's stays put between EMA updates."""
+        return self._cached(self._packs, (id(op), transposed, "winograd"), _pack_key(op, scale), self._build_winograd_filter,
+                            op, transposed, scale)
+
+    @staticmethod
+    def _build_winograd_filter(old, op, transposed, scale):
+        return ops.winograd_filter(op.spec, op.convs[0].weight.detach(), transposed, scale, out=old)
 
     def largest_tensor_bytes(self, Nb, H, W):
         """Bytes of the largest activation (or expanded-conv intermediate) a pass over an [Nb, *, H, W] input creates.  The conv

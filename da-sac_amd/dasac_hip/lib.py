@@ -78,7 +78,11 @@ PROTOTYPES = {
     "dasac_conv_gemm_stats_tiles": (_i, [_i, _i, _i]),
     "dasac_conv_gemm_stats": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_p, _p, _i, _i, _i, _i, _p, _sz, _p, _p]),
     "dasac_bn_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, C.c_double, _p, _i, _i, _l, _p, _p, _p, _p]),
-    "dasac_conv_pack_expanded": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "dasac_winograd_tiles": (_i, [_i, _i, _i, _i]),
+    "dasac_winograd_filter": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "dasac_winograd_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "dasac_winograd_output": (_i, [_p, _sz, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "dasac_conv_pack_expanded":(_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dasac_tap_gather": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "dasac_tap_scatter": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dasac_conv_wgrad_finish_expanded": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p]),

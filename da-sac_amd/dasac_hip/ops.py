@@ -292,6 +292,116 @@ def conv_dgrad(spec, dz, weights, in_hw, scale=None, res=None, mask=None, table=
     return relu_mask(dx, mask) if mask is not None else dx
 
 
+# ----------------------------------------------------------------------------------------------
+# Winograd F(2x2,3x3) for the wide dilated 3x3 convolutions (include/dasac_hip.h: dasac_winograd_*)
+# ----------------------------------------------------------------------------------------------
+# Algorithm of the forward / data-gradient GEMMs of an eligible convolution:
+#   "auto"    Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2), direct elsewhere;
+#   "direct"  the direct implicit GEMM everywhere.
+ALGORITHM = "auto"
+WINOGRAD_MIN_CHANNEL_PRODUCT = 512 * 512     # below it the two transforms cost more than the GEMMs save (layer3: DESIGN.md)
+_MAX_TENSOR_BYTES = (1 << 32) - 4096         # buffer-descriptor window of the kernels
+
+
+def set_conv_algorithm(mode):
+    global ALGORITHM
+    assert mode in ("auto", "direct"), mode
+    ALGORITHM = mode
+
+
+def winograd_ok(spec, transposed=False):
+    """True when the forward (transposed: the data-gradient) GEMM of `spec` has a Winograd form: one 3x3 branch, stride 1,
+    padding == dilation, gathered channels a multiple of 16, fp32 arithmetic."""
+    if len(spec.branches) != 1 or spec.stride != 1 or PRECISION != "fp32":
+        return False
+    kh, kw, d, p = spec.branches[0]
+    C = spec.cout if transposed else spec.cin
+    return kh == 3 and kw == 3 and d >= 1 and p == d and C % 16 == 0
+
+
+def winograd_routed(spec, transposed, Nb, H, W):
+    """The routing rule of the engine: eligible, wide enough to pay, the transformed tensors inside the 4 GiB window."""
+    if ALGORITHM != "auto" or not winograd_ok(spec, transposed) or spec.cin * spec.cout < WINOGRAD_MIN_CHANNEL_PRODUCT:
+        return False
+    T = L.load().dasac_winograd_tiles(Nb, H, W, spec.branches[0][2])
+    return T > 0 and 64 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES
+
+
+def winograd_filter(spec, weight, transposed, scale=None, out=None):
+    """U [16, Kpad, Mpad]: the 16 point matrices G g G^T of `weight` [Cout,Cin,3,3] (scale[co] folded in), each packed as
+    `conv_pack` packs a 1x1 convolution; transposed: rotated filter, channels swapped (the data gradient)."""
+    lib = L.load()
+    L.require_gpu(weight, scale)
+    M, K = (spec.cin, spec.cout) if transposed else (spec.cout, spec.cin)
+    shape = (16, lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M))
+    if out is None or tuple(out.shape) != shape:
+        out = torch.empty(shape, dtype=torch.float32, device=weight.device)
+    L.check(lib.dasac_winograd_filter(_c(weight).data_ptr(), L.ptr(scale), spec.cout, spec.cin, int(transposed), out.data_ptr(),
+                                      L.stream_ptr()), "dasac_winograd_filter")
+    return out
+
+
+_wino_tables = {}
+
+
+def _winograd_table(C, T, device):
+    """Gather table of the point GEMMs: a 1x1 convolution over C planes of 1 x T."""
+    key = (device.index, C, T)
+    t = _wino_tables.get(key)
+    if t is None:
+        if len(_wino_tables) > 64:
+            _wino_tables.clear()
+        t = _wino_tables[key] = conv_table(ConvSpec(C, C, [(1, 1, 1, 0)]), 1, T, False, device)
+    return t
+
+
+def winograd_output(y, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
+    """out [Nb,M,H,W] = epilogue(A^T Y A) of the point GEMMs' results y [16, M, T]: + shift, ReLU, ReLU pattern recorded into
+    `bits_out` or the elements whose bit in `mask_bits` is clear zeroed (both ReluBits of out's shape)."""
+    lib = L.load()
+    L.require_gpu(y, out, shift)
+    Nb, M, H, W = out.shape
+    assert y.is_contiguous() and out.is_contiguous() and y.dtype == torch.float32
+    for b in (mask_bits, bits_out):
+        assert b is None or b.shape == tuple(out.shape)
+    with PROFILE.span("winograd_output", 0.0, None, 4.0 * (y.numel() + out.numel())):
+        L.check(lib.dasac_winograd_output(y.data_ptr(), y.numel() * 4, Nb, M, H, W, int(dilation), L.ptr(shift), int(relu),
+                                          0 if mask_bits is None else mask_bits.words.data_ptr(),
+                                          0 if bits_out is None else bits_out.words.data_ptr(), out.data_ptr(), L.stream_ptr()),
+                "dasac_winograd_output")
+    return out
+
+
+def winograd_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None, gemm_schedule="auto"):
+    """out [Nb,M,H,W] = epilogue(conv3x3(x [Nb,C,H,W], dilation = padding)) with the transformed filter u = `winograd_filter`
+    (forward, or the data-gradient form with x = dz): input transform, 16 point GEMMs (`conv_gemm`), output transform.
+    The two transformed tensors [16, C, T] and [16, M, T] live in the stream's scratch buffer.
+    gemm_schedule: `conv_gemm`'s schedule for the point GEMMs; "auto" asks for the persistent stream-K kernel when a launch has
+    fewer tiles than the tile-per-block kernel has resident slots (layer4: 604 tiles on 256 CUs = 2.36 per CU, a CU with three
+    sets the time; equal K-ranges: 92 -> 96 TFLOP/s, profiles/winograd_layer4_ab.txt) and leaves the choice to the library otherwise."""
+    lib = L.load()
+    L.require_gpu(x, u, out)
+    Nb, C, H, W = x.shape
+    M = out.shape[1]
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (Nb, M, H, W)
+    assert tuple(u.shape) == (16, lib.dasac_conv_kpad(C), lib.dasac_conv_mpad(M)) and u.is_contiguous()
+    T = lib.dasac_winograd_tiles(Nb, H, W, int(dilation))
+    if T <= 0 or 64 * max(C, M) * T > _MAX_TENSOR_BYTES:
+        raise L.DasacError("winograd_conv: [16, {}, tiles] exceeds the 4 GiB buffer-descriptor window".format(max(C, M)))
+    v_elems, y_elems = 16 * C * T, 16 * M * T
+    ws = L.workspace(4 * (v_elems + y_elems), x.device)[:4 * (v_elems + y_elems)].view(torch.float32)
+    v, y = ws[:v_elems].view(16, C, T), ws[v_elems:v_elems + y_elems].view(16, M, T)
+    with PROFILE.span("winograd_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
+        L.check(lib.dasac_winograd_input(x.data_ptr(), Nb, C, H, W, int(dilation), v.data_ptr(), v_elems * 4, L.stream_ptr()),
+                "dasac_winograd_input")
+    table = _winograd_table(C, T, x.device)
+    if gemm_schedule == "auto":
+        gemm_schedule = 2 if ((M + 127) // 128) * ((T + 127) // 128) < 4 * L.EXPECTED_CUS else None
+    for pt in range(16):
+        conv_gemm(v[pt].view(1, C, 1, T), u[pt], table, y[pt].view(1, M, 1, T), (1, T), 1, M, C, schedule=gemm_schedule)
+    return winograd_output(y, out, dilation, shift, relu, mask_bits, bits_out)
+
+
 def dot_rows(spec):
     """Rows of the partial d-gamma dot term `conv_wgrad(dot=...)` fills (one per block of 64 input channels)."""
     return L.load().dasac_conv_wgrad_dot_rows(spec.cin, spec.taps)

@@ -175,6 +175,32 @@ int dasac_conv_wgrad_finish(const void* workspace, int Nb, int OH, int OW, int M
                             const float* w, const float* scale, float* dw, float* dot,
                             float* sum_dz, int Cin, int taps, int tap0, dasac_stream_t stream);
 
+/* Winograd F(2x2,3x3) evaluation of 3x3, stride-1 convolutions with padding == dilation (the 512 -> 512, dilation-4 conv2 of the
+ * layer4 bottlenecks, deeplabv2.py:65-66), forward and data gradient: 2.25 x fewer multiplies than the direct contraction, UNFUSED --
+ * three streaming kernels around SIXTEEN dasac_conv_gemm calls, no matrix kernel of its own.  The d*d dilation phases of the map
+ * are cut into 2x2-output tiles; T = dasac_winograd_tiles(Nb, H, W, dilation) of them in all (tile numbering: csrc/winograd_index.hpp).
+ *   dasac_winograd_filter  u = 16 packed matrices, one per Winograd point pt = 4a + b, each laid out as dasac_conv_pack lays out a
+ *                          1x1 convolution (dasac_conv_kpad(K) * dasac_conv_mpad(M) floats per point, padding written as zeros):
+ *                          U[pt] = (G g G^T)[a][b] with g = w[co][ci] * scale[co] (scale may be NULL).  transposed = 0: M = Cout,
+ *                          K = Cin (forward); transposed = 1: M = Cin, K = Cout and g rotated by 180 degrees (data gradient).
+ *   dasac_winograd_input   v [16][C][T] = B^T d B of every tile's 4x4 patch of x [Nb,C,H,W] (taps `dilation` apart, zero outside
+ *                          the image).  v_bytes >= 16*C*T*4.
+ *   point GEMMs (caller)   for pt in 0..15: dasac_conv_gemm(x = v + pt*C*T, packed = u + pt*Kpad*Mpad, table of a 1x1 convolution
+ *                          over planes of 1 x T, out = y + pt*M*T, Nb = 1, Cx = K = C, H = OH = 1, W = OW = T, no epilogue operands)
+ *   dasac_winograd_output  out [Nb,M,H,W] = epi(A^T Y A): + shift[m] (may be NULL), ReLU when `relu`; relu_bits_out (relu = 1)
+ *                          receives the pattern out > 0 and mask_bits zeroes the elements whose bit is clear, both in the layout of
+ *                          dasac_conv_gemm's bit masks (dasac_relu_bits_words(M, Nb*H*W) words); at most one of the two.
+ *                          Tiles that hang over the map edge store their in-image pixels only.  y_bytes >= 16*M*T*4.
+ * Rounding differs from the direct contraction (two transforms of additions in front of and behind the products): within a small
+ * multiple of its error against an exact convolution, not bit-equal to it. */
+int dasac_winograd_tiles(int Nb, int H, int W, int dilation);
+int dasac_winograd_filter(const float* w, const float* scale, int Cout, int Cin, int transposed, float* u,
+                          dasac_stream_t stream);
+int dasac_winograd_input(const float* x, int Nb, int C, int H, int W, int dilation, float* v, size_t v_bytes,
+                         dasac_stream_t stream);
+int dasac_winograd_output(const float* y, size_t y_bytes, int Nb, int M, int H, int W, int dilation, const float* shift,
+                          int relu, const uint32_t* mask_bits, uint32_t* relu_bits_out, float* out, dasac_stream_t stream);
+
 /* Tap-expanded evaluation of few-output-channel, many-tap convolutions -- the ASPP classifiers
  * (deeplabv2.py:101-116): Y[(tap,co)] = 1x1 GEMM over taps*Cp channels (dasac_conv_gemm with weights
  * from dasac_conv_pack_expanded), out = bias + sum_tap shift(Y) (dasac_tap_gather); backward:

@@ -1,0 +1,94 @@
+"""A/B of ONE layer4 conv2 (512 -> 512, 3x3, dilation 4, 8 crops of 97 x 97): the direct implicit GEMM against the Winograd
+F(2x2,3x3) path, forward (shift + ReLU + recorded bits) and data gradient (masked with recorded bits), as the engine issues them.
+
+    python tools/winograd_ab.py [--reps 3] [--iters 10] [--direct-only]
+
+Per repetition: `iters` back-to-back evaluations between one HIP event pair -> ms per conv, summing every launch that replaces
+the direct one (input transform + 16 point GEMMs + output transform).  A second pass splits the Winograd time per kernel with
+an event pair per launch (ops.PROFILE).  With DASAC_LIB naming an older build of the library and --direct-only, the direct
+figures are that build's (the A/B against the parent commit on the same box)."""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "da-sac_amd"))
+
+from dasac_hip import ops  # noqa: E402
+from dasac_hip import lib as L  # noqa: E402
+
+
+def timed(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--channels", type=int, default=512)
+    ap.add_argument("--size", type=int, default=97)
+    ap.add_argument("--dilation", type=int, default=4)
+    ap.add_argument("--direct-only", action="store_true")
+    ap.add_argument("--gemm-schedule", type=int, default=-1,
+                    help="schedule of the 16 point GEMMs: -1 what the engine uses (default), 0 the library's choice, 1 one block per tile, 2 stream-K")
+    args = ap.parse_args()
+    sched = {-1: "auto", 0: None}.get(args.gemm_schedule, args.gemm_schedule)
+    dev = torch.device("cuda", 0)
+    N, C, S, d = args.batch, args.channels, args.size, args.dilation
+    torch.manual_seed(0)
+    spec = ops.ConvSpec(C, C, [(3, 3, d, d)])
+    x = torch.randn(N, C, S, S, device=dev)
+    dz = torch.randn(N, C, S, S, device=dev)
+    w = torch.randn(C, C, 3, 3, device=dev) * (2.0 / (9 * C)) ** 0.5
+    scale, shift = torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev) * 0.1
+    out, dx = torch.empty_like(x), torch.empty_like(x)
+    bits, mask = ops.ReluBits(N, C, S, S, dev), ops.ReluBits(N, C, S, S, dev)
+    mask.words.random_(-2 ** 31, 2 ** 31 - 1)
+
+    of, ot = ops.gemm_order(spec, False), ops.gemm_order(spec, True)
+    tab_f, tab_t = ops.conv_table(spec, S, S, False, dev, of), ops.conv_table(spec, S, S, True, dev, ot)
+    pk_f, pk_t = ops.conv_pack(spec, [w], False, scale, order=of), ops.conv_pack(spec, [w], True, scale, order=ot)
+    legs = {
+        "forward direct": lambda: ops.conv_gemm(x, pk_f, tab_f, out, (S, S), 1, C, spec.K, 1, shift, None, None, True, bits_out=bits),
+        "dgrad   direct": lambda: ops.conv_gemm(dz, pk_t, tab_t, dx, (S, S), 1, C, spec.Kt, 1, None, None, mask, False),
+    }
+    if not args.direct_only:
+        u_f, u_t = ops.winograd_filter(spec, w, False, scale), ops.winograd_filter(spec, w, True, scale)
+        legs["forward winograd"] = lambda: ops.winograd_conv(x, u_f, out, d, shift, True, bits_out=bits, gemm_schedule=sched)
+        legs["dgrad   winograd"] = lambda: ops.winograd_conv(dz, u_t, dx, d, mask_bits=mask, gemm_schedule=sched)
+        legs["filter transform (per weight update, forward + dgrad)"] = lambda: (ops.winograd_filter(spec, w, False, scale, out=u_f),
+                                                                                 ops.winograd_filter(spec, w, True, scale, out=u_t))
+    print("library: {}   shape: {} x {} -> {} x {} x {}, dilation {}   {} iterations per repetition".format(
+        L.LIB_PATH, N, C, C, S, S, d, args.iters))
+    for name, fn in legs.items():
+        ms = [timed(fn, args.iters) for _ in range(args.reps)]
+        print("{:<58s} ms per conv: {}   spread {:.4f}".format(name, "  ".join("{:.4f}".format(v) for v in ms), max(ms) - min(ms)))
+    if not args.direct_only:
+        for name in ("forward winograd", "dgrad   winograd"):
+            legs[name]()
+            torch.cuda.synchronize()
+            ops.PROFILE.start()
+            for _ in range(args.iters):
+                legs[name]()
+            prof = ops.PROFILE.stop()
+            print(name + ", per-kernel split (event pair per launch):")
+            for k, v in sorted(prof.items()):
+                print("    {:<28s} {:2d} launches  {:.4f} ms per conv   {:.1f} TFLOP/s  {:.2f} TB/s algorithmic".format(
+                    k, v["launches"] // args.iters, v["seconds"] / args.iters * 1e3, v["flops"] / max(v["seconds"], 1e-12) / 1e12,
+                    v["bytes"] / max(v["seconds"], 1e-12) / 1e12))
+
+
+if __name__ == "__main__":
+    main()

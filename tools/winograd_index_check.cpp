@@ -1,0 +1,180 @@
+// Stand-alone host check of csrc/winograd_index.hpp: walks every offset the input and the output transform of winograd.hip form
+// for a list of shapes and requires each to lie inside its tensor, the tile numbering to be a bijection, and every output pixel
+// to belong to exactly one (tile, ey, ex).  Small shapes also touch heap arrays of the tensors' exact sizes at those offsets, so a
+// build with -fsanitize=address,undefined reports any access the arithmetic check itself would have missed.
+//
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -Ida-sac_amd/csrc tools/winograd_index_check.cpp -o wino_check && ./wino_check
+//
+// Host code only: never loaded into Python, never run on the GPU.
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "winograd_index.hpp"
+
+using namespace dasac::wino;
+
+static long long g_bad = 0;
+#define EXPECT(cond, ...)                          \
+  do {                                             \
+    if (!(cond)) {                                 \
+      if (g_bad++ < 10) {                          \
+        std::printf("FAIL %s: ", #cond);           \
+        std::printf(__VA_ARGS__);                  \
+        std::printf("\n");                         \
+      }                                            \
+    }                                              \
+  } while (0)
+
+static void check_div(int d, int limit) {
+  const Div f = make_div(d);
+  const int probes[] = {0, 1, d - 1, d, d + 1, 2 * d - 1, 2 * d, limit - 1, limit, limit / d * d, limit / d * d - 1};
+  for (int n : probes)
+    if (n >= 0) EXPECT(div(n, f) == n / d, "d=%d n=%d got %d", d, n, div(n, f));
+}
+
+static void check_shape(int N, int C, int M, int H, int W, int d, bool say = true) {
+  const Geom g = make_geom(N, H, W, d);
+  const long long x_bytes = 4ll * N * C * H * W, v_bytes = 4ll * 16 * C * g.T, y_bytes = 4ll * 16 * M * g.T, out_bytes = 4ll * N * M * H * W;
+  const int npix = N * H * W, w32 = (npix + 31) / 32;
+  EXPECT(x_bytes <= kMaxBytes && v_bytes <= kMaxBytes && y_bytes <= kMaxBytes && out_bytes <= kMaxBytes, "tensor too large");
+  // phase sizes against their definition
+  for (const Axis* a : {&g.ay, &g.ax}) {
+    int tiles = 0, samples = 0;
+    for (int p = 0; p < a->d; ++p) {
+      int cnt = 0;
+      for (int o = p; o < a->n; o += a->d) ++cnt;
+      EXPECT(phase_samples(*a, p) == cnt, "phase %d of n=%d d=%d: %d != %d", p, a->n, a->d, phase_samples(*a, p), cnt);
+      tiles += (cnt + 1) / 2;
+      samples += cnt;
+    }
+    EXPECT(tiles == a->tiles && samples == a->n, "n=%d d=%d: %d tiles, expected %d", a->n, a->d, a->tiles, tiles);
+    std::vector<int> seen(a->tiles, 0);
+    for (int p = 0; p < a->d; ++p)
+      for (int t = 0; t < (phase_samples(*a, p) + 1) / 2; ++t) {
+        const int gi = tile_encode(*a, p, t);
+        EXPECT(gi >= 0 && gi < a->tiles, "tile number %d of %d", gi, a->tiles);
+        if (gi < 0 || gi >= a->tiles) continue;
+        ++seen[gi];
+        int p2, t2;
+        tile_decode(*a, gi, p2, t2);
+        EXPECT(p2 == p && t2 == t, "decode(encode(%d,%d)) = (%d,%d)", p, t, p2, t2);
+      }
+    for (int gi = 0; gi < a->tiles; ++gi) EXPECT(seen[gi] == 1, "tile %d of axis n=%d d=%d named %d times", gi, a->n, a->d, seen[gi]);
+    check_div(a->d, a->n);
+  }
+  check_div(g.tiles_img, g.T);
+  check_div(g.ax.tiles, g.tiles_img);
+  check_div(g.HW, npix);
+  check_div(W, g.HW);
+
+  // small shapes: real arrays of the exact sizes, touched at every offset (what the sanitizers watch)
+  const bool touch = x_bytes + v_bytes + y_bytes + out_bytes < (96ll << 20);
+  std::vector<unsigned char> X, V, Y, O;
+  std::vector<unsigned> bits;
+  if (touch) {
+    X.assign(x_bytes, 0);
+    V.assign(v_bytes, 0);
+    Y.assign(y_bytes, 0);
+    O.assign(out_bytes, 0);
+    bits.assign((size_t)M * w32, 0u);
+  }
+  // channels walked: all of them when the arrays are touched, else the first and the last (offsets are monotonic in c)
+  std::vector<int> cs, ms;
+  for (int c = 0; c < C; ++c)
+    if (touch || c == 0 || c == C - 1) cs.push_back(c);
+  for (int m = 0; m < M; ++m)
+    if (touch || m == 0 || m == M - 1) ms.push_back(m);
+
+  // ---- input transform: every (c, tile): 16 gathered taps, 16 stores
+  std::vector<int> reads((size_t)N * H * W, 0);
+  for (int c : cs)
+    for (int tile = 0; tile < g.T; ++tile) {
+      int n, y0, x0;
+      tile_origin(g, tile, n, y0, x0);
+      EXPECT(n >= 0 && n < N && y0 >= 0 && y0 < H && x0 >= 0 && x0 < W, "tile %d -> image %d origin (%d,%d)", tile, n, y0, x0);
+      for (int ky = 0; ky < 4; ++ky)
+        for (int kx = 0; kx < 4; ++kx) {
+          const unsigned off = patch_offset(g, C, n, c, y0, x0, ky, kx);
+          const int y = y0 + (ky - 1) * d, x = x0 + (kx - 1) * d;
+          const bool inside = y >= 0 && y < H && x >= 0 && x < W;
+          EXPECT(inside == (off != kOutside), "tile %d tap (%d,%d): inside %d offset %u", tile, ky, kx, (int)inside, off);
+          if (off == kOutside) continue;
+          EXPECT((long long)off + 4 <= x_bytes && off % 4 == 0, "x offset %u of %lld", off, x_bytes);
+          EXPECT(off == 4u * (unsigned)(((n * C + c) * H + y) * W + x), "x offset %u is not (%d,%d,%d,%d)", off, n, c, y, x);
+          if (touch && (long long)off + 4 <= x_bytes) ++X[off];
+          if (c == cs[0]) ++reads[(size_t)(n * H + y) * W + x];
+        }
+      for (int pt = 0; pt < 16; ++pt) {
+        const unsigned off = point_offset(g, C, pt, c, tile);
+        EXPECT((long long)off + 4 <= v_bytes && off % 4 == 0, "v offset %u of %lld", off, v_bytes);
+        if (touch && (long long)off + 4 <= v_bytes) {
+          EXPECT(V[off] == 0, "v offset %u written twice", off);
+          V[off] = 1;
+        }
+      }
+    }
+  // every input pixel belongs to the 4x4 patches of exactly 2 x 2 tiles, fewer only next to the far edges
+  for (size_t i = 0; i < reads.size(); ++i) EXPECT(reads[i] >= 1 && reads[i] <= 4, "pixel %zu read %d times", i, reads[i]);
+  if (touch)
+    for (long long i = 0; i < v_bytes; i += 4) EXPECT(V[i] == 1, "v offset %lld never written", i);
+
+  // ---- output transform: every (m, pixel): 9 loads, one store, one bit
+  std::vector<int> tile_hits(g.T, 0);
+  for (int m : ms)
+    for (int pix = 0; pix < npix; ++pix) {
+      int n, rem, tile, ey, ex;
+      pixel_tile(g, pix, n, rem, tile, ey, ex);
+      EXPECT(n == pix / (H * W) && rem == pix % (H * W), "pixel %d -> image %d rem %d", pix, n, rem);
+      EXPECT(tile >= 0 && tile < g.T && (ey | ex) >= 0 && ey <= 1 && ex <= 1, "pixel %d -> tile %d (%d,%d)", pix, tile, ey, ex);
+      if (tile < 0 || tile >= g.T) continue;
+      int n2, y0, x0;
+      tile_origin(g, tile, n2, y0, x0);
+      EXPECT(n2 == n && y0 + ey * d == rem / W && x0 + ex * d == rem % W, "pixel %d is not output (%d,%d) of tile %d", pix, ey, ex, tile);
+      if (m == ms[0]) ++tile_hits[tile];
+      for (int j = 0; j < 3; ++j)
+        for (int k = 0; k < 3; ++k) {
+          const int pt = (ey + j) * 4 + ex + k;
+          EXPECT(pt >= 0 && pt < 16, "point %d", pt);
+          const unsigned off = point_offset(g, M, pt, m, tile);
+          EXPECT((long long)off + 4 <= y_bytes && off % 4 == 0, "y offset %u of %lld", off, y_bytes);
+          if (touch && (long long)off + 4 <= y_bytes) ++Y[off];
+        }
+      const unsigned off = out_offset(g, M, n, m, rem);
+      EXPECT((long long)off + 4 <= out_bytes && off == 4u * (unsigned)((n * M + m) * H * W + rem), "out offset %u of %lld", off, out_bytes);
+      if (touch && (long long)off + 4 <= out_bytes) {
+        EXPECT(O[off] == 0, "out offset %u written twice", off);
+        O[off] = 1;
+      }
+      const long long word = (long long)m * w32 + (pix >> 5);
+      EXPECT(word < (long long)M * w32, "bit word %lld of %lld", word, (long long)M * w32);
+      if (touch && word < (long long)M * w32) bits[word] |= 1u << (pix & 31);
+    }
+  for (int t = 0; t < g.T; ++t) EXPECT(tile_hits[t] >= 1 && tile_hits[t] <= 4, "tile %d holds %d output pixels", t, tile_hits[t]);
+  if (touch)
+    for (long long i = 0; i < out_bytes; i += 4) EXPECT(O[i] == 1, "out offset %lld never written", i);
+  if (say)
+    std::printf("N=%d C=%d M=%d %dx%d d=%d: %d x %d tiles per image, T=%d%s\n", N, C, M, H, W, d, g.ay.tiles, g.ax.tiles, g.T,
+                touch ? " (arrays touched)" : "");
+}
+
+int main() {
+  // the shapes of tests/test_gpu_winograd.py, forward (C = Cin, M = Cout) and data gradient (swapped), and the layer4 conv2 of the step
+  const int shapes[][6] = {{2, 32, 128, 9, 7, 4}, {1, 32, 128, 11, 13, 2}, {2, 16, 128, 10, 10, 1}, {1, 16, 128, 97, 97, 4},
+                           {8, 512, 512, 97, 97, 4}};
+  for (const auto& s : shapes) {
+    check_shape(s[0], s[1], s[2], s[3], s[4], s[5]);
+    if (s[1] != s[2]) check_shape(s[0], s[2], s[1], s[3], s[4], s[5]);
+  }
+  // a sweep of small maps and dilations: empty phases, one-tile phases, every parity of q
+  for (int d = 1; d <= 5; ++d)
+    for (int h = 1; h <= 12; ++h)
+      for (int w = 1; w <= 12; w += 3) check_shape(1, 2, 3, h, w, d, false);
+  const Geom big = make_geom(8, 97, 97, 4);
+  if (big.ay.tiles != 49 || big.ax.tiles != 49 || big.T != 19208) {
+    std::printf("FAIL: 8 x 97 x 97, d = 4 must give 49 x 49 tiles per image, 19208 in all\n");
+    ++g_bad;
+  }
+  std::printf("winograd index check: %lld bad\n", g_bad);
+  return g_bad ? 1 : 0;
+}
