@@ -234,6 +234,9 @@ int dasac_conv_wgrad_finish_expanded(const void* workspace, int Nb, int OH, int 
  *     (optional) receives gscale[0] * d loss / d logits (gscale: device scalar = upstream
  *     gradient of the loss, NULL = 1); per_class (optional) [C] as sac.py:138-145 (order-independent Q28 fixed-point
  *     accumulation: per-pixel values are clamped to |ce| <= 4096 there; the loss itself is not clamped).
+ *     Labels: 255 is the ignore index, and EVERY label outside [0, C) is treated like it (F.cross_entropy raises on
+ *     those): such a pixel carries no loss, no gradient (its dlogits are exactly 0) and no per_class term, but still
+ *     counts in the mean's divisor.  dasac_ce_loss_bwd_low follows the same rule.
  * dasac_warp_affine       grid_sample(x, affine_grid(theta), bilinear, zeros, align_corners=False)
  * dasac_warp_pool         sac.py:289-305 with _avg_pool (mode 0, :238-269) or _minentropy_pool
  *     (mode 1, :218-236): probs [N*T,C,H,W] -> pooled [N,C,H,W], mask [N,H,W]; `aligned`
