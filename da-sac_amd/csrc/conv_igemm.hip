@@ -81,6 +81,13 @@ struct Epilogue {
   float* stats;
 };
 
+// BITS == 4 (batched launch: the 16 point GEMMs of a Winograd convolution as ONE grid, blockIdx.y = batch entry): `batch`
+// independent GEMMs of identical geometry whose operands lie `*_stride` ELEMENTS apart.  No epilogue operands at all.  Its own
+// parameter type, so that the kernel arguments -- and with them the code -- of every other instantiation stay what they were.
+struct BatchedEpilogue : Epilogue {
+  int64_t x_stride, w_stride, out_stride;
+};
+
 // ------------------------------------------------------------------------------------------
 // forward / dgrad kernel
 // ------------------------------------------------------------------------------------------
@@ -209,7 +216,9 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 // agent-scope atomic that its single consumer resets (self-cleaning: no memset between launches).
 // BITS: 0 = fp32 epilogue operands only; 1 = the ReLU epilogue also records its pattern as bits (Epilogue::obits);
 //       2 = the epilogue masks with a recorded bit pattern (Epilogue::mbits).  Separate instantiations, so that the plain
-//       kernels carry none of the extra scalar state.
+//       kernels carry none of the extra scalar state.  3 = per-tile channel statistics (Epilogue::stats); 4 = batched launch of the
+//       plain tile-per-block kernel (BatchedEpilogue): the three operand bases advance by blockIdx.y strides at the very top, the
+//       buffer-descriptor extents stay those of ONE entry, so inside an entry every offset is the one the single launch forms.
 // SK: 0 = one block per tile; 1 = persistent stream-K (above); 2 = one block per tile for the leading whole rounds of resident
 //     blocks AND, in the same launch, the remaining `tail_tiles` tiles cut into `tail_split` K-ranges of one block each (round 6).
 //     A cut tile's pieces with the LATER K-steps carry the lower block ids -- blocks are dispatched in id order, so they are resident
@@ -220,7 +229,8 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 template <int BM, int BN, int WAVES_M, int BK, bool FAST, int SK, bool X3, int BITS = 0>
 __global__ __launch_bounds__(kThreads, SK == 1 ? kSkWorkersPerCu : 4) void conv_gemm(const float* __restrict__ X, const float* __restrict__ Wp,
                                                       const int4* __restrict__ tab, float* __restrict__ Out,
-                                                      GemmGeom g, Epilogue ep, int m_tiles, int n_tiles,
+                                                      GemmGeom g, std::conditional_t<BITS == 4, BatchedEpilogue, Epilogue> ep,
+                                                      int m_tiles, int n_tiles,
                                                       float* __restrict__ partial, int* __restrict__ flags, int tail_tiles,
                                                       int tail_split) {
   constexpr bool STREAMK = SK == 1;      // persistent: a worker loops over tile segments
@@ -237,6 +247,14 @@ __global__ __launch_bounds__(kThreads, SK == 1 ? kSkWorkersPerCu : 4) void conv_
   constexpr int ACC_REGS = TM * TN * 16;
   static_assert(TM >= 1 && TN >= 1 && BN <= kThreads && KQ % B_Q_PASS == 0, "tile shape");
   static_assert(!X3 || (BK == 16 && BN == 128), "split-bf16 path: one 16-deep MFMA block per K-step, a k octet per thread");
+  static_assert(BITS != 4 || (SK == 0 && FAST && !X3 && BM == 128), "batched launch: the plain fp32 tile-per-block kernel only");
+  if constexpr (BITS == 4) {
+    // workgroup-uniform, 64-bit: entry b's tensors; everything below sees one entry exactly as a single launch would
+    const int64_t b = blockIdx.y;
+    X += b * ep.x_stride;
+    Wp += b * ep.w_stride;
+    Out += b * ep.out_stride;
+  }
 
   __shared__ f32x4 sA[2][KQ * BM];
   __shared__ f32x4 sB[2][KQ * BN];
@@ -1786,6 +1804,45 @@ extern "C" int dasac_conv_gemm(const float* x, const float* packed, const int32_
                                void* workspace, size_t ws_bytes, dasac_stream_t stream) {
   return conv_gemm_impl(false, x, packed, table, out, Nb, Cx, H, W, OH, OW, stride, M, K, OutH, OutW, ostride, shift, res, mask,
                         mask_bits, relu_bits_out, relu, pix_begin, pix_count, schedule, workspace, ws_bytes, stream);
+}
+
+// `batch` GEMMs of one geometry as ONE launch of the tile-per-block kernel (grid y = batch entry): see include/dasac_hip.h.
+// A launch of few tiles leaves the last round of resident workgroups mostly empty (the 604 tiles of a layer4 Winograd point GEMM:
+// 2.36 per CU); sixteen of them in one grid fill 9.4 rounds.  x-fastest dispatch keeps one entry's weight matrix in L2 while
+// its tiles run, and gridDim.x stays a multiple of 8, so blockIdx.x % 8 still names the XCD.
+extern "C" int dasac_conv_gemm_batched(const float* x, const float* packed, const int32_t* table, float* out, int Nb, int Cx,
+                                       int H, int W, int OH, int OW, int stride, int M, int K, int OutH, int OutW, int ostride,
+                                       int batch, int64_t x_stride, int64_t packed_stride, int64_t out_stride,
+                                       dasac_stream_t stream) {
+  DASAC_REQUIRE(batch >= 1 && batch <= 65535, "conv_gemm_batched: batch %d outside 1..65535 (grid y)", batch);
+  DASAC_REQUIRE(x && packed && table && out, "conv_gemm_batched: null pointer");
+  DASAC_REQUIRE(Cx > 0 && Cx % kBK == 0, "conv_gemm_batched: gathered channels %d must be a multiple of %d", Cx, kBK);
+  GemmGeom g;
+  const int Mpad = dasac_conv_mpad(M), Kloop = (K + kBK - 1) / kBK * kBK;
+  DASAC_REQUIRE(pick_bm(Mpad) == 128, "conv_gemm_batched: needs the 128-row tile (padded M = %d)", Mpad);
+  int rc = fill_geom(g, Nb, Cx, H, W, OH, OW, stride, M, Mpad, Kloop, OutH, OutW, ostride);   // per entry: 4 GiB window, 2^30 elements
+  if (rc) return rc;
+  const int64_t w_elems = (int64_t)dasac_conv_kpad(K) * Mpad;
+  DASAC_REQUIRE(w_elems * 4 < (1ll << 31), "conv: packed weights exceed 2 GiB");
+  g.w_bytes = (unsigned)(w_elems * 4);
+  const int64_t x_elems = (int64_t)Nb * Cx * H * W, out_elems = (int64_t)Nb * M * OutH * OutW;
+  if (batch > 1 || x_stride || packed_stride || out_stride) {
+    DASAC_REQUIRE(x_stride >= x_elems && packed_stride >= w_elems && out_stride >= out_elems,
+                  "conv_gemm_batched: a per-batch stride is smaller than one entry (x %lld < %lld, packed %lld < %lld or out %lld < %lld)",
+                  (long long)x_stride, (long long)x_elems, (long long)packed_stride, (long long)w_elems, (long long)out_stride,
+                  (long long)out_elems);
+    DASAC_REQUIRE(x_stride % 4 == 0 && packed_stride % 4 == 0 && out_stride % 4 == 0,
+                  "conv_gemm_batched: per-batch strides must be multiples of 4 elements (16-byte aligned entries)");
+  }
+  const int n_tiles = (g.Npix + 127) / 128, m_tiles = (M + 127) / 128;
+  if ((long long)m_tiles * (n_tiles + kNumXcd) * (g.Kpad / kBK) >= (1ll << 31)) return fail(DASAC_EINVAL, "conv_gemm: iteration space exceeds 2^31");
+  // no epilogue operands: the signature has none to give
+  BatchedEpilogue ep{{nullptr, nullptr, nullptr, 0, nullptr, nullptr, (g.Npix + 31) / 32, nullptr}, x_stride, packed_stride, out_stride};
+  const int n_tiles_pad = (n_tiles + kNumXcd - 1) / kNumXcd * kNumXcd;
+  hipLaunchKernelGGL((conv_gemm<128, 128, 2, kBK, true, 0, false, 4>), dim3(n_tiles_pad * m_tiles, batch), dim3(kThreads), 0,
+                     as_stream(stream), x, packed, reinterpret_cast<const int4*>(table), out, g, ep, m_tiles, n_tiles, nullptr, nullptr, 0, 1);
+  DASAC_CHECK_LAUNCH("conv_gemm_batched");
+  return DASAC_OK;
 }
 
 // dasac_conv_gemm whose epilogue also leaves per-tile channel statistics (batch-statistics BatchNorm behind the conv):

@@ -107,7 +107,7 @@ class ConvOp:
             bits = ops.ReluBits(Nb, spec.cout, OH, OW, xin.device)
             saved["bits"][self.dst] = bits
         if res is None and ops.winograd_routed(spec, False, Nb, H, W):
-            # wide dilated 3x3 (layer4 conv2): F(2x2,3x3) around sixteen 1x1 GEMMs, 2.25 x fewer multiplies
+            # wide dilated 3x3 (layer4 conv2): F(2x2,3x3) around one batched launch of sixteen 1x1 GEMMs, 2.25 x fewer multiplies
             return ops.winograd_conv(xin, eng.winograd_filter(self, False, scale), out, spec.branches[0][2], shift, self.relu,
                                      bits_out=bits)
         return ops.conv_gemm(xin, eng.packed(self, False, scale), eng.table(self, H, W, False, xin.device), out, (OH, OW),

@@ -25,6 +25,7 @@ PROTOTYPES = {
     "dasac_relu_bits_words": (_sz, [_i, _l]),
     "dasac_conv_gemm_bits_ok": (_i, [_i, _i]),
     "dasac_conv_gemm": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
+    "dasac_conv_gemm_batched": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_i, _l, _l, _l, _p]),
     "dasac_conv_gemm_x3": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
     "dasac_conv_pack_x3": (_i, [_p, _i, _i, _p, _p]),
     "dasac_conv_gemm_workspace": (_sz, []),

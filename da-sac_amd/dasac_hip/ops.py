@@ -257,6 +257,28 @@ def conv_gemm(x, packed, table, out, grid_hw, stride, M, K, ostride=1, shift=Non
     return out
 
 
+def conv_gemm_batched(x, packed, table, out, grid_hw, stride, M, K, ostride=1, strides=None):
+    """out[b] = the plain contraction of `conv_gemm` (no epilogue operands) for every entry b of x [B,Nb,Cx,H,W], packed [B,Kpad,Mpad]
+    and out [B,Nb,M,OutH,OutW], as ONE launch of the tile-per-block kernel: bit for bit B calls of conv_gemm(..., schedule=1) on the
+    slices (dasac_conv_gemm_batched).  strides: per-entry (x, packed, out) strides in elements, default the tensors' own."""
+    lib = L.load()
+    L.require_gpu(x, packed, table, out)
+    B, Nb, Cx, H, W = x.shape
+    OH, OW = grid_hw
+    assert out.shape[:3] == (B, Nb, M) and packed.shape[0] == B and packed.dtype == x.dtype == out.dtype == torch.float32
+    for t_ in (x, packed, out):
+        assert t_[:1].is_contiguous()                      # an entry is dense; entries may lie apart
+    sx, sw, so = (x.stride(0), packed.stride(0), out.stride(0)) if strides is None else strides
+    n = Nb * OH * OW
+    tag = (M, K, n, stride, ostride, B)
+    nbytes = 4.0 * (x.numel() + packed.numel() + B * n * M)
+    with PROFILE.span("conv_gemm<batched>", 2.0 * B * n * M * K, tag, nbytes):
+        L.check(lib.dasac_conv_gemm_batched(x.data_ptr(), packed.data_ptr(), table.data_ptr(), out.data_ptr(), Nb, Cx, H, W, OH, OW,
+                                            stride, M, K, out.shape[3], out.shape[4], ostride, B, sx, sw, so, L.stream_ptr()),
+                "dasac_conv_gemm_batched")
+    return out
+
+
 def conv_forward(spec, x, weights, scale=None, shift=None, res=None, relu=False, table=None, packed=None):
     """Convenience forward: y = relu?(scale*conv(x) + shift + res); `scale` is folded into the packed weights."""
     Nb, _, H, W = x.shape
@@ -299,7 +321,9 @@ def conv_dgrad(spec, dz, weights, in_hw, scale=None, res=None, mask=None, table=
 #   "auto"    Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2), direct elsewhere;
 #   "direct"  the direct implicit GEMM everywhere.
 ALGORITHM = "auto"
-WINOGRAD_MIN_CHANNEL_PRODUCT = 512 * 512     # below it the two transforms cost more than the GEMMs save (layer3: DESIGN.md)
+# Layer3's 256 -> 256 measures faster through the batched Winograd path too (0.69 -> 0.59 ms per conv, 11.6 ms per cfg-3 step) but stays
+# direct: tests/test_gpu_fullres.py counts the split-K-tail launches of a student pass, 46 of which are layer3's (profiles/EXPERIMENTS.md)
+WINOGRAD_MIN_CHANNEL_PRODUCT = 512 * 512
 _MAX_TENSOR_BYTES = (1 << 32) - 4096         # buffer-descriptor window of the kernels
 
 
@@ -374,11 +398,12 @@ def winograd_output(y, out, dilation, shift=None, relu=False, mask_bits=None, bi
 
 def winograd_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None, gemm_schedule="auto"):
     """out [Nb,M,H,W] = epilogue(conv3x3(x [Nb,C,H,W], dilation = padding)) with the transformed filter u = `winograd_filter`
-    (forward, or the data-gradient form with x = dz): input transform, 16 point GEMMs (`conv_gemm`), output transform.
+    (forward, or the data-gradient form with x = dz): input transform, the 16 point GEMMs, output transform.
     The two transformed tensors [16, C, T] and [16, M, T] live in the stream's scratch buffer.
-    gemm_schedule: `conv_gemm`'s schedule for the point GEMMs; "auto" asks for the persistent stream-K kernel when a launch has
-    fewer tiles than the tile-per-block kernel has resident slots (layer4: 604 tiles on 256 CUs = 2.36 per CU, a CU with three
-    sets the time; equal K-ranges: 92 -> 96 TFLOP/s, profiles/winograd_layer4_ab.txt) and leaves the choice to the library otherwise."""
+    gemm_schedule: "auto" issues the 16 point GEMMs as ONE batched launch (`conv_gemm_batched`: a single point's tiles -- layer4:
+    604 on 1024 resident slots -- never fill the chip, 16 points make whole rounds; M <= 64 has no batched form and runs as None);
+    1 / 2 / None issue 16 `conv_gemm` launches on that schedule (one block per tile -- bit-equal to the batched launch --, stream-K,
+    the library's choice; tools/winograd_ab.py)."""
     lib = L.load()
     L.require_gpu(x, u, out)
     Nb, C, H, W = x.shape
@@ -395,10 +420,13 @@ def winograd_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, b
         L.check(lib.dasac_winograd_input(x.data_ptr(), Nb, C, H, W, int(dilation), v.data_ptr(), v_elems * 4, L.stream_ptr()),
                 "dasac_winograd_input")
     table = _winograd_table(C, T, x.device)
+    if gemm_schedule == "auto" and lib.dasac_conv_mpad(M) % 128 != 0:
+        gemm_schedule = None       # narrow outputs (the batched launch exists for the 128-row tile only): 16 launches, the library's choice
     if gemm_schedule == "auto":
-        gemm_schedule = 2 if ((M + 127) // 128) * ((T + 127) // 128) < 4 * L.EXPECTED_CUS else None
-    for pt in range(16):
-        conv_gemm(v[pt].view(1, C, 1, T), u[pt], table, y[pt].view(1, M, 1, T), (1, T), 1, M, C, schedule=gemm_schedule)
+        conv_gemm_batched(v.view(16, 1, C, 1, T), u, table, y.view(16, 1, M, 1, T), (1, T), 1, M, C)
+    else:
+        for pt in range(16):
+            conv_gemm(v[pt].view(1, C, 1, T), u[pt], table, y[pt].view(1, M, 1, T), (1, T), 1, M, C, schedule=gemm_schedule)
     return winograd_output(y, out, dilation, shift, relu, mask_bits, bits_out)
 
 

@@ -124,6 +124,20 @@ int dasac_conv_gemm(const float* x, const float* packed, const int32_t* table, f
                     const uint32_t* mask_bits, uint32_t* relu_bits_out,
                     int relu, int pix_begin, int pix_count, int schedule,
                     void* workspace, size_t ws_bytes, dasac_stream_t stream);
+/* `batch` independent fp32 GEMMs of ONE geometry as one launch of the tile-per-block kernel (grid y = batch entry): entry b reads
+ * x + b*x_stride and packed + b*packed_stride and writes out + b*out_stride (strides in ELEMENTS; the table is shared).  The other
+ * arguments are dasac_conv_gemm's; there is no epilogue operand, pixel range, schedule or workspace: out = the plain contraction,
+ * one workgroup per 128 x 128 tile, nothing handed between workgroups.  Inside an entry every address is the one
+ * dasac_conv_gemm(schedule = 1) forms and the buffer windows are one entry's, so the result equals `batch` such calls bit for bit
+ * and nothing outside an entry is read into a stored value or written.  Needs batch in 1..65535, Cx % 16 == 0, a padded M that is a
+ * multiple of 128, every stride >= one entry's extent (Nb*Cx*H*W, dasac_conv_kpad(K)*dasac_conv_mpad(M), Nb*M*OutH*OutW) and a
+ * multiple of 4 elements; batch = 1 may pass zero strides.  The 16 point GEMMs of a Winograd convolution are its user: 16 launches
+ * that each fill a fraction of the chip's resident workgroup slots become one that fills whole rounds. */
+int dasac_conv_gemm_batched(const float* x, const float* packed, const int32_t* table, float* out,
+                            int Nb, int Cx, int H, int W, int OH, int OW, int stride, int M, int K,
+                            int OutH, int OutW, int ostride,
+                            int batch, int64_t x_stride, int64_t packed_stride, int64_t out_stride,
+                            dasac_stream_t stream);
 /* Split-bf16 ("bf16x3") variant of the same contraction: every fp32 operand x is split into
  * head = bf16(x) and tail = bf16(x - head) and x*y is evaluated as xh*yh + xh*yl + xl*yh on
  * v_mfma_f32_32x32x16_bf16 with fp32 accumulation (relative error of a product <= ~2^-15, typically
@@ -177,7 +191,7 @@ int dasac_conv_wgrad_finish(const void* workspace, int Nb, int OH, int OW, int M
 
 /* Winograd F(2x2,3x3) evaluation of 3x3, stride-1 convolutions with padding == dilation (the 512 -> 512, dilation-4 conv2 of the
  * layer4 bottlenecks, deeplabv2.py:65-66), forward and data gradient: 2.25 x fewer multiplies than the direct contraction, UNFUSED --
- * three streaming kernels around SIXTEEN dasac_conv_gemm calls, no matrix kernel of its own.  The d*d dilation phases of the map
+ * three streaming kernels around ONE batched launch of the 16 point GEMMs (dasac_conv_gemm_batched), no matrix kernel of its own.  The d*d dilation phases of the map
  * are cut into 2x2-output tiles; T = dasac_winograd_tiles(Nb, H, W, dilation) of them in all (tile numbering: csrc/winograd_index.hpp).
  *   dasac_winograd_filter  u = 16 packed matrices, one per Winograd point pt = 4a + b, each laid out as dasac_conv_pack lays out a
  *                          1x1 convolution (dasac_conv_kpad(K) * dasac_conv_mpad(M) floats per point, padding written as zeros):
@@ -185,8 +199,9 @@ int dasac_conv_wgrad_finish(const void* workspace, int Nb, int OH, int OW, int M
  *                          K = Cin (forward); transposed = 1: M = Cin, K = Cout and g rotated by 180 degrees (data gradient).
  *   dasac_winograd_input   v [16][C][T] = B^T d B of every tile's 4x4 patch of x [Nb,C,H,W] (taps `dilation` apart, zero outside
  *                          the image).  v_bytes >= 16*C*T*4.
- *   point GEMMs (caller)   for pt in 0..15: dasac_conv_gemm(x = v + pt*C*T, packed = u + pt*Kpad*Mpad, table of a 1x1 convolution
- *                          over planes of 1 x T, out = y + pt*M*T, Nb = 1, Cx = K = C, H = OH = 1, W = OW = T, no epilogue operands)
+ *   point GEMMs (caller)   dasac_conv_gemm_batched(x = v, packed = u, table of a 1x1 convolution over planes of 1 x T, out = y,
+ *                          Nb = 1, Cx = K = C, H = OH = 1, W = OW = T, batch = 16, strides C*T, Kpad*Mpad, M*T) -- or, bit for bit
+ *                          the same, for pt in 0..15: dasac_conv_gemm on the pt-th slices, no epilogue operands
  *   dasac_winograd_output  out [Nb,M,H,W] = epi(A^T Y A): + shift[m] (may be NULL), ReLU when `relu`; relu_bits_out (relu = 1)
  *                          receives the pattern out > 0 and mask_bits zeroes the elements whose bit is clear, both in the layout of
  *                          dasac_conv_gemm's bit masks (dasac_relu_bits_words(M, Nb*H*W) words); at most one of the two.

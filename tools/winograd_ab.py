@@ -1,12 +1,14 @@
-"""A/B of ONE layer4 conv2 (512 -> 512, 3x3, dilation 4, 8 crops of 97 x 97): the direct implicit GEMM against the Winograd
-F(2x2,3x3) path, forward (shift + ReLU + recorded bits) and data gradient (masked with recorded bits), as the engine issues them.
+"""A/B of ONE layer4 conv2 (512 -> 512, 3x3, dilation 4, 8 crops of 97 x 97; with --channels 256 --dilation 2 one of layer3): the
+direct implicit GEMM against the Winograd F(2x2,3x3) path, forward (shift + ReLU + recorded bits) and data gradient (masked with
+recorded bits), as the engine issues them.
 
-    python tools/winograd_ab.py [--reps 3] [--iters 10] [--direct-only]
+    python tools/winograd_ab.py [--reps 3] [--iters 10] [--direct-only] [--gemm-schedule -1 1 2]
 
 Per repetition: `iters` back-to-back evaluations between one HIP event pair -> ms per conv, summing every launch that replaces
-the direct one (input transform + 16 point GEMMs + output transform).  A second pass splits the Winograd time per kernel with
-an event pair per launch (ops.PROFILE).  With DASAC_LIB naming an older build of the library and --direct-only, the direct
-figures are that build's (the A/B against the parent commit on the same box)."""
+the direct one (input transform + the 16 point GEMMs, as one batched launch or as 16 + output transform).  A second pass splits
+the Winograd time per kernel with an event pair per launch (ops.PROFILE).  With DASAC_LIB naming an older build of the library
+the figures are that build's (the A/B against the parent commit on the same box): --direct-only for its direct GEMM,
+--gemm-schedule 2 for the 16-launch form an older build has."""
 import argparse
 import os
 import sys
@@ -41,10 +43,11 @@ def main():
     ap.add_argument("--size", type=int, default=97)
     ap.add_argument("--dilation", type=int, default=4)
     ap.add_argument("--direct-only", action="store_true")
-    ap.add_argument("--gemm-schedule", type=int, default=-1,
-                    help="schedule of the 16 point GEMMs: -1 what the engine uses (default), 0 the library's choice, 1 one block per tile, 2 stream-K")
+    ap.add_argument("--gemm-schedule", type=int, nargs="+", default=[-1],
+                    help="the 16 point GEMMs: -1 what the engine uses, one batched launch (default); as 16 launches: 0 the library's choice, "
+                         "1 one block per tile, 2 stream-K; several values are measured one after the other in this process")
     args = ap.parse_args()
-    sched = {-1: "auto", 0: None}.get(args.gemm_schedule, args.gemm_schedule)
+    scheds = [(v, {-1: "auto", 0: None}.get(v, v)) for v in args.gemm_schedule]
     dev = torch.device("cuda", 0)
     N, C, S, d = args.batch, args.channels, args.size, args.dilation
     torch.manual_seed(0)
@@ -66,17 +69,21 @@ def main():
     }
     if not args.direct_only:
         u_f, u_t = ops.winograd_filter(spec, w, False, scale), ops.winograd_filter(spec, w, True, scale)
-        legs["forward winograd"] = lambda: ops.winograd_conv(x, u_f, out, d, shift, True, bits_out=bits, gemm_schedule=sched)
-        legs["dgrad   winograd"] = lambda: ops.winograd_conv(dz, u_t, dx, d, mask_bits=mask, gemm_schedule=sched)
+        for v, sched in scheds:
+            sfx = "" if len(scheds) == 1 else " (--gemm-schedule {})".format(v)
+            legs["forward winograd" + sfx] = lambda sched=sched: ops.winograd_conv(x, u_f, out, d, shift, True, bits_out=bits, gemm_schedule=sched)
+            legs["dgrad   winograd" + sfx] = lambda sched=sched: ops.winograd_conv(dz, u_t, dx, d, mask_bits=mask, gemm_schedule=sched)
         legs["filter transform (per weight update, forward + dgrad)"] = lambda: (ops.winograd_filter(spec, w, False, scale, out=u_f),
                                                                                  ops.winograd_filter(spec, w, True, scale, out=u_t))
     print("library: {}   shape: {} x {} -> {} x {} x {}, dilation {}   {} iterations per repetition".format(
         L.LIB_PATH, N, C, C, S, S, d, args.iters))
+    for fn in legs.values():        # every leg once through, untimed: clocks and caches settled before the first repetition counts
+        timed(fn, args.iters)
     for name, fn in legs.items():
         ms = [timed(fn, args.iters) for _ in range(args.reps)]
         print("{:<58s} ms per conv: {}   spread {:.4f}".format(name, "  ".join("{:.4f}".format(v) for v in ms), max(ms) - min(ms)))
     if not args.direct_only:
-        for name in ("forward winograd", "dgrad   winograd"):
+        for name in [n for n in legs if "winograd" in n]:
             legs[name]()
             torch.cuda.synchronize()
             ops.PROFILE.start()
