@@ -1208,6 +1208,67 @@ def mask_counts(scores, label_maps, gt, counts=None, ignore_index=255, num_class
     return counts
 
 
+CONFUSION_MAX_BINS = 32
+
+
+def confusion_counts(scores, label_maps, gt, confusion=None, reliability=None, bins=0, logits_layers=(), ignore_index=255,
+                     num_classes=None):
+    """The joint tables of `mask_counts`' pass in ONE launch (include/dasac_hip.h: dasac_confusion_counts).  scores: up to 4 fp32
+    [B,C,H,W] tensors (arg-max, first maximum wins); label_maps: up to 2 [B,H,W] maps, int64 or uint8 each (255 = no label); gt int64
+    [B,H,W].  Accumulates into `confusion` (int64 [L,C+1,C+1], scores first, then label maps; row = ground truth, column =
+    prediction, index C = no class; allocated zeroed when None).  With `bins` > 0 (or a `reliability` tensor, whose shape gives the
+    bins) it also accumulates into `reliability` (int64 [len(scores),C,bins,2]: arg-max class, bin of the winning confidence, miss /
+    hit); `logits_layers` lists the indices into `scores` that hold logits -- their confidence is the soft-max maximum -- the others
+    hold probabilities.  With label maps only, C comes from `confusion` or `num_classes`.  Returns (confusion, reliability or None)."""
+    lib = L.load()
+    scores, label_maps = list(scores or ()), list(label_maps or ())
+    L.require_gpu(gt, confusion, reliability, *scores, *label_maps)
+    n_layers = len(scores) + len(label_maps)
+    if n_layers == 0 or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
+        raise L.DasacError("confusion_counts takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
+            MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
+    if gt.dtype != torch.int64 or gt.dim() != 3:
+        raise L.DasacError("confusion_counts: gt must be int64 [B,H,W] (got {} {})".format(gt.dtype, tuple(gt.shape)))
+    B, H, W = gt.shape
+    Cn = scores[0].shape[1] if scores else (confusion.shape[1] - 1 if confusion is not None else num_classes)
+    if Cn is None:
+        raise L.DasacError("confusion_counts: label maps alone do not tell the class count; pass confusion or num_classes")
+    for s in scores:
+        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
+            raise L.DasacError("confusion_counts: a score tensor must be float32 {} (got {} {})".format((B, Cn, H, W), s.dtype, tuple(s.shape)))
+    for m in label_maps:
+        if m.dtype not in (torch.int64, torch.uint8) or tuple(m.shape) != (B, H, W):
+            raise L.DasacError("confusion_counts: a label map must be int64 or uint8 {} (got {} {})".format((B, H, W), m.dtype, tuple(m.shape)))
+    if confusion is None:
+        confusion = torch.zeros((n_layers, Cn + 1, Cn + 1), dtype=torch.int64, device=gt.device)
+    elif confusion.dtype != torch.int64 or tuple(confusion.shape) != (n_layers, Cn + 1, Cn + 1) or not confusion.is_contiguous():
+        raise L.DasacError("confusion_counts accumulates into a contiguous int64 [{},{},{}] tensor (got {} {})".format(
+            n_layers, Cn + 1, Cn + 1, confusion.dtype, tuple(confusion.shape)))
+    bins = int(bins)
+    if reliability is not None:
+        bins = int(reliability.shape[2]) if reliability.dim() == 4 else -1          # -1: refused below
+    logits_layers = sorted(set(int(i) for i in logits_layers))
+    if bins:
+        if not scores or not 1 <= bins <= CONFUSION_MAX_BINS:
+            raise L.DasacError("confusion_counts: a reliability table needs a score tensor and 1..{} bins (got {} tensors, {} bins)".format(
+                CONFUSION_MAX_BINS, len(scores), bins))
+        if any(i < 0 or i >= len(scores) for i in logits_layers):
+            raise L.DasacError("confusion_counts: logits_layers {} names no score tensor of {}".format(logits_layers, len(scores)))
+        if reliability is None:
+            reliability = torch.zeros((len(scores), Cn, bins, 2), dtype=torch.int64, device=gt.device)
+        elif reliability.dtype != torch.int64 or tuple(reliability.shape) != (len(scores), Cn, bins, 2) or not reliability.is_contiguous():
+            raise L.DasacError("confusion_counts accumulates into a contiguous int64 [{},{},bins,2] reliability tensor (got {} {})".format(
+                len(scores), Cn, reliability.dtype, tuple(reliability.shape)))
+    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
+    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
+    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
+    u8_mask = sum(1 << i for i, m in enumerate(label_maps) if m.dtype == torch.uint8)
+    L.check(lib.dasac_confusion_counts(*sp, *mp, u8_mask, gt.data_ptr(), B, Cn, H * W, int(ignore_index), confusion.data_ptr(),
+                                       L.ptr(reliability), bins, sum(1 << i for i in logits_layers), L.stream_ptr()),
+            "dasac_confusion_counts")
+    return confusion, reliability
+
+
 VIS_IMAGE, VIS_LABELS, VIS_SCORES, VIS_CONF = 0, 1, 2, 3
 
 

@@ -444,12 +444,15 @@ def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="me
         return ops.infer_fuse(sources, flips, (H, W), mode, lut, want_conf, want_probs)
 
 
-def validation_iou(net, batches, num_classes=19, scales=None, flip=False):
+def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confusion=False):
     """mIoU over (image, label) batches: argmax + per-class tp/fp/fn in one kernel pass per batch
     (train.py:339-469, utils/metrics.py:9-53); counts are all-reduced when a process group exists.
     With `scales` (or `flip`) the prediction is infer_label_maps_ms's label map (scales defaults to (1.0,) when only `flip` is
     set) and the counts come from the label-layer counter (ops.mask_counts, as `validation` counts `teacher_labels`); the uint8
-    map is widened to the int64 that counter reads, the one torch operation of that path."""
+    map is widened to the int64 that counter reads, the one torch operation of that path.
+    With `confusion` the pass is ops.confusion_counts instead -- it reads the uint8 map as it is -- the counts follow from the
+    matrix (counts_from_confusion: the same integers) and the return value is (mIoU, iou, matrix int64 [C+1,C+1] on the host: row =
+    ground truth, column = prediction, index C = no class; see summarise_confusion)."""
     import torch.distributed as dist
     from dasac_hip import ops
     core = net.module if hasattr(net, "module") else net
@@ -461,17 +464,24 @@ def validation_iou(net, batches, num_classes=19, scales=None, flip=False):
         for image, gt in batches:
             if multi_scale:
                 maps, _, _ = infer_label_maps_ms(net, image, (1.0,) if scales is None else scales, flip)
-                counts = ops.mask_counts([], [maps.to(torch.int64)], gt, counts, num_classes=num_classes)
+                if confusion:
+                    counts, _ = ops.confusion_counts([], [maps], gt, counts, num_classes=num_classes)
+                else:
+                    counts = ops.mask_counts([], [maps.to(torch.int64)], gt, counts, num_classes=num_classes)
             else:
                 _, logits_up = core(image)
-                counts = ops.iou_counts(logits_up, gt, counts)
+                if confusion:
+                    counts, _ = ops.confusion_counts([logits_up], [], gt, counts)
+                else:
+                    counts = ops.iou_counts(logits_up, gt, counts)
     core.train(was)
-    if multi_scale and counts is not None:
+    if (multi_scale or confusion) and counts is not None:
         counts = counts[0]
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(counts)
-    iou, _, _ = summarise_iou(counts)
-    return float(iou.mean()), iou
+    matrix = counts.cpu() if confusion else None
+    iou, _, _ = summarise_iou(counts_from_confusion(matrix) if confusion else counts)
+    return (float(iou.mean()), iou, matrix) if confusion else (float(iou.mean()), iou)
 
 
 def summarise_iou(counts):
@@ -480,6 +490,103 @@ def summarise_iou(counts):
     tp, fp, fn = (counts[i].to(torch.float32).cpu() for i in range(3))
     floor = torch.tensor(1e-3)
     return tp / torch.maximum(floor, fn + fp + tp), tp / torch.maximum(floor, tp + fp), tp / torch.maximum(floor, tp + fn)
+
+
+def counts_from_confusion(matrix):
+    """(tp, fp, fn) of a confusion matrix int64 [C+1,C+1] (row = ground truth, column = prediction, index C = no class; leading
+    layer dimensions are kept): tp[c] = M[c][c], fp[c] = sum_r M[r][c] - M[c][c], fn[c] = sum_k M[c][k] - M[c][c] for c < C -- int64
+    [..., 3, C] on the host, the integers ops.mask_counts counts (integer bookkeeping on a small host table)."""
+    import numpy as np
+    M = matrix.detach().cpu().numpy()
+    C = M.shape[-1] - 1
+    tp = np.diagonal(M, axis1=-2, axis2=-1)[..., :C]
+    return torch.from_numpy(np.stack([tp, M[..., :, :C].sum(-2) - tp, M[..., :C, :].sum(-1) - tp], -2).astype(np.int64))
+
+
+def _share(num, den):
+    """num / den in float64 with 0 where den is 0."""
+    num, den = num.to(torch.float64), den.to(torch.float64)
+    return torch.where(den > 0, num / den.clamp_min(1.0), torch.zeros_like(num))
+
+
+def summarise_confusion(matrix, ignore_classes=(), top=10):
+    """Reading of one confusion matrix int64 [C+1,C+1] (host or device; the result is on the host).  Returns a namespace:
+      by_gt, by_pred   the matrix divided by its ground-truth row sums / prediction column sums, float64; a zero row (column) stays 0;
+      pixel_accuracy   correct pixels over the pixels whose ground truth is a class (a prediction of "no class" is wrong);
+      fw_iou           sum_c freq_c * IoU_c with freq_c the class's share of those pixels and IoU_c = tp / (tp + fp + fn);
+      top              the `top` largest off-diagonal entries [(gt, pred, pixels, share of the gt row)], largest first, ties by
+                       (gt, pred); index C stands for "no class".
+    Classes in `ignore_classes` leave the accuracy, the frequencies of fw_iou and, as row or column, the top list; every class's
+    IoU is still computed on the whole matrix, as the class-subset means of `validation` are."""
+    from types import SimpleNamespace
+    M = matrix.detach().cpu().to(torch.int64)
+    C = M.shape[0] - 1
+    rows, cols = M.sum(1), M.sum(0)
+    by_gt, by_pred = _share(M, rows[:, None].expand_as(M)), _share(M, cols[None, :].expand_as(M))
+    ignore = set(int(i) for i in ignore_classes)
+    keep = torch.tensor([c for c in range(C) if c not in ignore], dtype=torch.int64)
+    tp, fp, fn = counts_from_confusion(M)
+    labelled = rows[keep].sum()
+    accuracy = float(_share(tp[keep].sum(), labelled))
+    fw_iou = float((_share(rows[keep], labelled.expand(len(keep))) * _share(tp, tp + fp + fn)[keep]).sum())
+    entries = [(int(M[r, c]), r, c) for r in range(C + 1) for c in range(C + 1)
+               if r != c and r not in ignore and c not in ignore and int(M[r, c]) > 0]
+    entries.sort(key=lambda t: (-t[0], t[1], t[2]))
+    worst = [(r, c, n, float(by_gt[r, c])) for n, r, c in entries[:top]]
+    return SimpleNamespace(by_gt=by_gt, by_pred=by_pred, pixel_accuracy=accuracy, fw_iou=fw_iou, top=worst)
+
+
+def pseudo_label_audit(labels_matrix, teacher_matrix):
+    """What the pseudo-label thresholds do per class, from the confusion matrices of `teacher_labels` (the thresholded label map,
+    255 = rejected = column C) and `teacher_refined` (the same teacher before thresholding).  float64 [C] each, 0 where a class has
+    no pixel:
+      coverage           share of the class's ground-truth pixels that received any label: 1 - M[c][C] / sum_k M[c][k];
+      precision          of the pixels labelled c, the share whose ground truth is c: M[c][c] / sum_r M[r][c];
+      teacher_recall     M_t[c][c] / sum_k M_t[c][k] of the unthresholded teacher;
+      teacher_precision  M_t[c][c] / sum_r M_t[r][c]."""
+    from types import SimpleNamespace
+    Ml, Mt = labels_matrix.detach().cpu().to(torch.int64), teacher_matrix.detach().cpu().to(torch.int64)
+    C = Ml.shape[0] - 1
+    rows = Ml[:C].sum(1)
+    return SimpleNamespace(coverage=_share(rows - Ml[:C, C], rows), precision=_share(torch.diagonal(Ml)[:C], Ml[:, :C].sum(0)),
+                           teacher_recall=_share(torch.diagonal(Mt)[:C], Mt[:C].sum(1)),
+                           teacher_precision=_share(torch.diagonal(Mt)[:C], Mt[:, :C].sum(0)))
+
+
+def summarise_reliability(table):
+    """Reading of one reliability table int64 [C,n_bins,2] (arg-max class, confidence bin, miss / hit).  Returns a namespace with,
+    per class, pixels int64 [C,n_bins], accuracy float64 [C,n_bins] (hits / pixels, 0 for an empty bin) and ece float64 [C]; and over
+    all classes overall_pixels [n_bins], overall_accuracy [n_bins], overall_ece (float).  The expected calibration error is
+    sum_b pixels_b / pixels * |accuracy_b - (b + 0.5) / n_bins|: it takes the bin MIDPOINT for the bin's confidence, because the table
+    keeps no sum of confidences -- an approximation, off by up to half a bin width (0.5 / n_bins) from the usual definition."""
+    from types import SimpleNamespace
+    R = table.detach().cpu().to(torch.int64)
+    n_bins = R.shape[1]
+    mid = (torch.arange(n_bins, dtype=torch.float64) + 0.5) / n_bins
+
+    def read(hit, pixels):
+        acc = _share(hit, pixels)
+        total = pixels.sum(-1, keepdim=True)
+        return acc, (_share(pixels, total.expand_as(pixels)) * (acc - mid).abs()).sum(-1)
+    pixels = R.sum(-1)
+    acc, ece = read(R[..., 1], pixels)
+    all_acc, all_ece = read(R[..., 1].sum(0), pixels.sum(0))
+    return SimpleNamespace(pixels=pixels, accuracy=acc, ece=ece, overall_pixels=pixels.sum(0), overall_accuracy=all_acc,
+                           overall_ece=float(all_ece))
+
+
+def format_confusion(matrix, names):
+    """Fixed-width text table of a confusion matrix int64 [C+1,C+1] for the log: one row per ground-truth class (`names`, C of them,
+    then "none"), one column per prediction, pixel counts."""
+    M = matrix.detach().cpu().to(torch.int64)
+    names = [str(n) for n in names] + ["none"]
+    assert len(names) == M.shape[0] == M.shape[1], (len(names), tuple(M.shape))
+    width = max(6, len(str(int(M.max()))))
+    head = max(len("gt \\ pred"), max(len(n) for n in names))
+    lines = [" ".join(["gt \\ pred".ljust(head)] + [n[:width].rjust(width) for n in names])]
+    for n, row in zip(names, M.tolist()):
+        lines.append(" ".join([n.ljust(head)] + [str(v).rjust(width) for v in row]))
+    return "\n".join(lines)
 
 
 def compute_sample_weights(net, batches, num_images, lut=None, teacher=False, scales=None, flip=False):
@@ -526,6 +633,7 @@ def compute_sample_weights(net, batches, num_images, lut=None, teacher=False, sc
 # --------------------------------------------------------------------------------------------------
 VALIDATION_SCORE_LAYERS = ("logits_up", "teacher_init", "teacher_refined")      # through argmax(., 1), train.py:394-395
 VALIDATION_LABEL_LAYERS = ("teacher_labels",)                                   # label maps as they are, 255 = no label (:396-397)
+VALIDATION_LOGITS_LAYERS = ("logits_up", "teacher_init")                        # logits; `teacher_refined` holds probabilities
 
 
 def validation_batches(loader, max_iter=None):
@@ -565,7 +673,8 @@ def summarise_validation(counts, ignore_classes=()):
     return per_class, mean, score
 
 
-def validation(net, loader, step="source", group_size=None, max_iter=None, ignore_classes=(), num_classes=19, num_groups=None):
+def validation(net, loader, step="source", group_size=None, max_iter=None, ignore_classes=(), num_classes=19, num_groups=None,
+               confusion=False, reliability_bins=0):
     """`Trainer.validation` (train.py:339-469) with its step function (`step` :119-155 or `_step_target` :211-250, train=False):
     eval mode under no_grad (the previous mode is restored), loss means, one (tp, fp, fn) table per mask layer, the per-class and
     class-subset summaries and the checkpoint score.  Neither the teacher nor the class prior is updated.
@@ -588,7 +697,15 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     checkpoint_score = max over layers of mIoU.  The reference computes the score on its main process only and returns 0.0
     elsewhere; here EVERY rank returns the same value (each holds the summed counts) -- save on rank 0 only as before.
     Not reproduced: metrics.py:30 overwrites the prediction in place at ignored pixels (nothing reads it afterwards), and the
-    reference's float32 counters, which stop being exact past 2^24 pixels per class -- the counts here are exact int64."""
+    reference's float32 counters, which stop being exact past 2^24 pixels per class -- the counts here are exact int64.
+
+    Beyond the reference, opt-in: with `confusion` or `reliability_bins` > 0 the one launch per batch is `ops.confusion_counts`
+    instead, and the namespace's `confusion` {layer: int64 [C+1,C+1]} (row = ground truth, column = prediction, index C = no class:
+    summarise_confusion, pseudo_label_audit, format_confusion) and, with bins, `reliability` {score layer: int64 [C,bins,2]}
+    (arg-max class, confidence bin, miss / hit: summarise_reliability; `logits_up` and `teacher_init` are binned by their soft-max
+    maximum, `teacher_refined` by its winning probability) are filled; both are empty dicts otherwise.  `counts` then follows from
+    the matrices (counts_from_confusion) and holds the same integers, so every other field is unchanged.  The tables share one
+    device buffer: they are summed over ranks and copied to the host as `table` is, once."""
     from types import SimpleNamespace
     import torch.distributed as dist
     from dasac_hip import ops
@@ -598,7 +715,8 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     rank, world = _dist_state(None, None)
     was = core.training
     core.eval()
-    layers, table, rows, keys = None, None, [], None
+    joint, bins = bool(confusion) or int(reliability_bins) > 0, int(reliability_bins)
+    layers, table, rows, keys, matrices, rel = None, None, [], None, None, None
     try:
         with torch.no_grad():
             for batch in validation_batches(loader, max_iter):
@@ -614,12 +732,21 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
                     layers = ([k for k in VALIDATION_SCORE_LAYERS if k in outs], [k for k in VALIDATION_LABEL_LAYERS if k in outs])
                     keys = sorted(losses)
                 scores, maps = [outs[k] for k in layers[0]], [outs[k] for k in layers[1]]
-                table = ops.mask_counts(scores, maps, gt, table, num_classes=num_classes)
+                if joint:
+                    if table is None:               # one buffer: [L][C+1][C+1] matrices, then [Ls][C][bins][2] reliability tables
+                        n_mat, side = len(scores) + len(maps), num_classes + 1
+                        table = torch.zeros(n_mat * side * side + len(scores) * num_classes * bins * 2, dtype=torch.int64, device=device)
+                        matrices = table[:n_mat * side * side].view(n_mat, side, side)
+                        rel = table[n_mat * side * side:].view(len(scores), num_classes, bins, 2) if bins > 0 else None
+                    logits = [i for i, k in enumerate(layers[0]) if k in VALIDATION_LOGITS_LAYERS]
+                    ops.confusion_counts(scores, maps, gt, matrices, rel, logits_layers=logits)
+                else:
+                    table = ops.mask_counts(scores, maps, gt, table, num_classes=num_classes)
                 rows.append(torch.cat([losses[k].detach().mean().reshape(1) for k in keys]))
     finally:
         core.train(was)
     if table is None:
-        return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0)
+        return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0, confusion={}, reliability={})
     names = layers[0] + layers[1]
     loss_rows = torch.stack(rows)
     multi = dist.is_available() and dist.is_initialized() and world > 1
@@ -633,10 +760,20 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
             dist.all_reduce(loss_rows)
             loss_rows = loss_rows / world
     table, loss_rows = table.cpu(), loss_rows.cpu().tolist()
+    conf_tables, rel_tables = {}, {}
+    if joint:
+        side = num_classes + 1
+        matrices = table[:len(names) * side * side].view(len(names), side, side)
+        conf_tables = {name: matrices[i] for i, name in enumerate(names)}
+        if bins > 0:
+            rel = table[len(names) * side * side:].view(len(layers[0]), num_classes, bins, 2)
+            rel_tables = {name: rel[i] for i, name in enumerate(layers[0])}
+        table = counts_from_confusion(matrices)
     counts = {name: table[i] for i, name in enumerate(names)}
     per_class, mean, score = summarise_validation(counts, ignore_classes)
     losses = {k: stat_mean([row[i] for row in loss_rows]) for i, k in enumerate(keys)}
-    return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score)
+    return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score,
+                           confusion=conf_tables, reliability=rel_tables)
 
 
 # --------------------------------------------------------------------------------------------------

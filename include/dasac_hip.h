@@ -522,6 +522,27 @@ int dasac_mask_counts(const float* scores0, const float* scores1, const float* s
                       const int64_t* labels0, const int64_t* labels1, const int64_t* gt, int B, int C, int64_t HW,
                       int ignore_index, int64_t* counts, dasac_stream_t stream);
 
+/* Joint tables of the same pass: which class is taken for which, and how often a confidence is right.  The layer slots are those
+ * of dasac_mask_counts -- up to 4 score tensors fp32 [B,C,HW] (arg-max, first maximum wins), up to 2 label maps [B,HW], NULL slots
+ * skipped, layers numbered over the non-NULL slots, scores first -- but a label map is int64 or, with bit i of `labels_u8_mask`
+ * set for slot labels<i>, uint8 at any address (the maps dasac_infer_fuse writes).  gt: int64 [B,HW].
+ *   confusion: int64 [L][C+1][C+1], ACCUMULATED into; row = ground truth, column = prediction; a value inside [0, C) is its own
+ *     index, every other value (a label map's 255, gt == -1, anything out of range) is index C, "no class".  A pixel with
+ *     gt == ignore_index is skipped for every output, and that is checked first.  Hence tp[c] = M[c][c], fp[c] = sum_r M[r][c] -
+ *     M[c][c], fn[c] = sum_k M[c][k] - M[c][c] (c < C) are dasac_mask_counts' counts bit for bit, and sum M = the pixels not ignored.
+ *   reliability: int64 [Ls][C][n_bins][2] over the Ls score layers, ACCUMULATED into, or NULL (then nothing of it is computed):
+ *     [l][p][b][h] with p the arg-max class, h = (p == gt) and b the bin of the winning confidence v -- the winning score itself
+ *     when bit l of `softmax_mask` is clear (the layer holds probabilities), 1.0f / sum_c expf(x_c - max_c x) in fp32 when it is set
+ *     (the layer holds logits); b = !(v > 0) ? 0 : min(n_bins - 1, (int)(v * n_bins)) with an fp32 multiply: NaN and 0 fall in bin
+ *     0, v >= 1 in the last.  1 <= n_bins <= 32.  sum_b [l][p][b][1] = M_l[p][p], sum_b [l][p][b][0] = sum_r M_l[r][p] - M_l[p][p].
+ * Integer adds only: exact and bit-identical from run to run.  C <= 64.  No load leaves a tensor; pointers need the alignment of
+ * their element type only.  No workspace.  One launch (two when C is close to 64, every slot is used and the tables of all
+ * layers exceed one workgroup's LDS). */
+int dasac_confusion_counts(const float* scores0, const float* scores1, const float* scores2, const float* scores3,
+                           const void* labels0, const void* labels1, int labels_u8_mask, const int64_t* gt, int B, int C,
+                           int64_t HW, int ignore_index, int64_t* confusion, int64_t* reliability, int n_bins, int softmax_mask,
+                           dasac_stream_t stream);
+
 /* Per-image class statistics for importance-sampled target selection (tools/compute_IS_weights.py:58-83, on the device):
  * counts[b][v] += number of pixels of image b with value v, v in 0..255 (value 255 is counted too; callers drop it).
  * labels: [B][HW] uint8, any alignment (an unaligned head and a tail of any length per image are read byte by byte, the
