@@ -1163,6 +1163,143 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad(const float* __restric
   }
 }
 
+// Batched weight gradient over plain matrices (the 16 point contractions of a Winograd weight gradient as ONE grid, blockIdx.y =
+// batch entry):  P[split][b][m][c] = sum_{t in split} A[b][m][t] * B[b][c][t],  A [batch][M][T], B [batch][C][T] row-major, entries
+// a_stride / b_stride ELEMENTS apart.  Per entry this is the QUAD case of conv_wgrad above -- the same 128 x 128 tile, LDS layout,
+// four-pixels-per-lane loader, MFMA loop and XCD-contiguous block order -- with what plain matrices make unnecessary left out: no tap,
+// no image boundary (host: M, C multiples of 128 and T, the split length and the strides multiples of 4, so a lane's quad lies
+// wholly inside its row and its split or wholly outside, and an outside quad reads zeros through the poison offset).  A kernel of its
+// own, so that conv_wgrad's instantiations compile to the code they had.  The pixel splits are chosen over batch x m_tiles x k_tiles
+// tiles: one entry alone would be cut into many short splits (layer4: 16 tiles -> 48 splits of 13 K-steps; batched: 256 tiles x 3
+// splits of 200).  Fixed summation order, no atomics.  Psum[split][m] = the split's row sums of entry `sum_entry` of A (k tile 0).
+struct WgradBatch {
+  int M, C, T;
+  int m_tiles, k_tiles, n_splits, pix_per_split;
+  int sum_entry;                   // entry whose row sums go to Psum (the Winograd point that is the tile's pixel sum)
+  int64_t a_stride, b_stride;
+};
+
+__global__ __launch_bounds__(kThreads, 3) void conv_wgrad_batched(const float* __restrict__ A, const float* __restrict__ B,
+                                                                float* __restrict__ P, float* __restrict__ Psum, WgradBatch w) {
+  constexpr int BM = 128, BN = 128, WAVES_M = 2, WAVES_N = 2;
+  constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
+  constexpr int TM = WM / 32, TN = WN / 32;
+  constexpr int AQ = BM / 32, BQ = BN / 32;
+  __shared__ __attribute__((aligned(16))) float sA[BM * kWgPitch];
+  __shared__ __attribute__((aligned(16))) float sB[BN * kWgPitch];
+
+  const int n_blocks = w.m_tiles * w.k_tiles * w.n_splits;
+  const int per_xcd = (n_blocks + kNumXcd - 1) / kNumXcd;
+  const int lb = ((int)blockIdx.x % kNumXcd) * per_xcd + (int)blockIdx.x / kNumXcd;
+  if (lb >= n_blocks) return;
+  const int entry = blockIdx.y;
+  const int tile = lb % (w.m_tiles * w.k_tiles), split = lb / (w.m_tiles * w.k_tiles);
+  const int m_tile = tile % w.m_tiles, k_tile = tile / w.m_tiles;
+  const int m0 = m_tile * BM, kb0 = k_tile * BN;
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+  const int li = lane & 31, lh = lane >> 5;
+  const int pq = t & 7, prow4 = t >> 3;                    // loader: pixel quad of the step, row within a 32-row pass
+
+  // one entry's window each: inside an entry every offset is below M*T (C*T) elements, host-checked to fit 31 bits of bytes
+  const __amdgpu_buffer_rsrc_t ra = make_rsrc(A + (size_t)entry * w.a_stride, (unsigned)(w.M * w.T) * 4u);
+  const __amdgpu_buffer_rsrc_t rb = make_rsrc(B + (size_t)entry * w.b_stride, (unsigned)(w.C * w.T) * 4u);
+
+  const int p_begin = split * w.pix_per_split;
+  const int p_end = min(p_begin + w.pix_per_split, w.T);
+  const int steps = (p_end - p_begin + kWgPix - 1) / kWgPix;
+  const bool do_sums = (k_tile == 0) && (entry == w.sum_entry);
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  f32x4 qa[AQ], qb[BQ];
+  float qsum[AQ];
+#pragma unroll
+  for (int i = 0; i < AQ; ++i) qsum[i] = 0.f;
+  int pix = p_begin + 4 * pq;                              // first pixel of this thread's quad (advanced by kWgPix per step)
+  // 16-byte loads: the poison is 2^31, not kPoison -- an entry's window is below 2^31 bytes (host), so all four dwords of a poisoned
+  // quad lie past it without the offset wrapping
+  constexpr unsigned kQuadPoison = 0x80000000u;
+#define DASAC_WGB_LOAD()                                                                             \
+  {                                                                                                  \
+    const unsigned v = pix < p_end ? (unsigned)(prow4 * w.T + pix) * 4u : kQuadPoison;               \
+    _Pragma("unroll") for (int i = 0; i < AQ; ++i) qa[i] = buf_f32x4(ra, v, (m0 + i * 32) * w.T * 4); \
+    _Pragma("unroll") for (int i = 0; i < BQ; ++i) qb[i] = buf_f32x4(rb, v, (kb0 + i * 32) * w.T * 4); \
+    if (do_sums) {                                                                                   \
+      _Pragma("unroll") for (int i = 0; i < AQ; ++i) qsum[i] += (qa[i].x + qa[i].y) + (qa[i].z + qa[i].w); \
+    }                                                                                                \
+    pix += kWgPix;                                                                                   \
+  }
+#define DASAC_WGB_STORE()                                                                            \
+  {                                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < AQ; ++i)                                                   \
+      *reinterpret_cast<f32x4*>(&sA[(prow4 + i * 32) * kWgPitch + 4 * pq]) = qa[i];                  \
+    _Pragma("unroll") for (int i = 0; i < BQ; ++i)                                                   \
+      *reinterpret_cast<f32x4*>(&sB[(prow4 + i * 32) * kWgPitch + 4 * pq]) = qb[i];                  \
+  }
+  if (steps > 0) {
+    DASAC_WGB_LOAD();
+    DASAC_WGB_STORE();
+  }
+  __syncthreads();
+  for (int s = 0; s < steps; ++s) {
+    if (s + 1 < steps) DASAC_WGB_LOAD();
+    const float* a_base = &sA[(wm * WM + li) * kWgPitch + 4 * lh];
+    const float* b_base = &sB[(wn * WN + li) * kWgPitch + 4 * lh];
+#pragma unroll
+    for (int gq = 0; gq < kWgPix / 8; ++gq) {
+      f32x4 a[TM], b[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(a_base + i * 32 * kWgPitch + 8 * gq);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(b_base + j * 32 * kWgPitch + 8 * gq);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+    if (s + 1 < steps) {
+      DASAC_WGB_STORE();
+      __syncthreads();
+    }
+  }
+#undef DASAC_WGB_LOAD
+#undef DASAC_WGB_STORE
+  if (do_sums) {
+    // the 8 lanes of a row hold its 32 pixels (4 each): butterfly over the three low lane bits
+#pragma unroll
+    for (int i = 0; i < AQ; ++i) {
+      float v = qsum[i];
+#pragma unroll
+      for (int o = 4; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (pq == 0) Psum[(size_t)split * w.M + m0 + prow4 + i * 32] = v;
+    }
+  }
+  // partial slab [split][entry][M][C], c contiguous
+  float* slab = P + ((size_t)split * gridDim.y + entry) * w.M * w.C;
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int k = kb0 + wn * WN + j * 32 + li;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int rg = 0; rg < 16; ++rg) {
+        const int m = m0 + wm * WM + i * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * lh;
+        slab[(size_t)m * w.C + k] = acc[i][j][rg];
+      }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // small helpers: gather table, weight packing, wgrad slab reduction
 // ------------------------------------------------------------------------------------------
@@ -1887,19 +2024,7 @@ static int wgrad_bn(int Cx) { return (Cx % 128 != 0 && Cx % 64 == 0) ? 64 : 128;
 // 109.2 to 114.0 ms (123.1 -> 117.9 TFLOP/s): occupancy is not what the pixel loop lacks.  Nor is it the dZ loads of the 3x3
 // layers: dZ through the four-pixels-per-lane loader (dwordx4 + ds_write_b128, the gathered operand unchanged) gives 109.6 vs
 // 109.1 ms.
-static int wgrad_splits(int Mpad, int Kpad, int Npix, int BM, int BNk = 128) {
-  const int tiles = (Mpad / BM) * (Kpad / BNk);
-  const int slots = kNumCu * 3;
-  // At least 256 pixels (8 K-steps) per split.  Rounds 1-3 asked for 1024: at batch 2 (cfg-2: 18 818 pixels) that capped the 16-tile
-  // 1x1 layers at 19 splits = 304 blocks for 768 slots; measured in round 4 (profiles/r4_wgrad_split_granularity.txt, cfg-2):
-  // 1024 -> 512 -> 256 pixels: weight gradients 18.7 -> 16.3 -> 15.4 ms/step (90 -> 103 -> 109 TFLOP/s).  Large batches are
-  // unaffected (the cap of 64 splits binds first).
-  constexpr int kMinPix = 256;
-  int max_splits = (Npix + kMinPix - 1) / kMinPix;
-  // few tiles x many pixels (layer1 / stem: 2 tiles, 298k..1.2M pixels): more splits, or 128 blocks would face 768 slots
-  const int cap = (tiles < 12 && Npix >= 200000) ? (slots + tiles - 1) / tiles : 64;   // measured: no gain at 97x97 resolution
-  if (max_splits > cap) max_splits = cap;
-  if (max_splits < 1) max_splits = 1;
+static int fill_rounds(int tiles, int max_splits, int slots) {   // the split count in 1..max_splits whose blocks fill whole rounds
   int best = 1;
   double best_eff = 0.0;
   for (int sp = 1; sp <= max_splits; ++sp) {
@@ -1912,6 +2037,21 @@ static int wgrad_splits(int Mpad, int Kpad, int Npix, int BM, int BNk = 128) {
     }
   }
   return best;
+}
+
+static int wgrad_splits(int Mpad, int Kpad, int Npix, int BM, int BNk = 128) {
+  const int tiles = (Mpad / BM) * (Kpad / BNk);
+  const int slots = kNumCu * 3;
+  // At least 256 pixels (8 K-steps) per split.  Rounds 1-3 asked for 1024: at batch 2 (cfg-2: 18 818 pixels) that capped the 16-tile
+  // 1x1 layers at 19 splits = 304 blocks for 768 slots; measured in round 4 (profiles/r4_wgrad_split_granularity.txt, cfg-2):
+  // 1024 -> 512 -> 256 pixels: weight gradients 18.7 -> 16.3 -> 15.4 ms/step (90 -> 103 -> 109 TFLOP/s).  Large batches are
+  // unaffected (the cap of 64 splits binds first).
+  constexpr int kMinPix = 256;
+  int max_splits = (Npix + kMinPix - 1) / kMinPix;
+  // few tiles x many pixels (layer1 / stem: 2 tiles, 298k..1.2M pixels): more splits, or 128 blocks would face 768 slots
+  const int cap = (tiles < 12 && Npix >= 200000) ? (slots + tiles - 1) / tiles : 64;   // measured: no gain at 97x97 resolution
+  if (max_splits > cap) max_splits = cap;
+  return fill_rounds(tiles, max_splits, slots);
 }
 
 extern "C" size_t dasac_conv_wgrad_workspace(int Nb, int OH, int OW, int M, int K) {
@@ -2012,6 +2152,46 @@ extern "C" int dasac_conv_wgrad_finish(const void* workspace, int Nb, int OH, in
     hipLaunchKernelGGL(wgrad_reduce, dim3(Cin / 64, M), dim3(256), 0, as_stream(stream), P, Psum, splits, Mpad, Kpad, w, scale, dw, dot,
                        sum_dz, Cin, taps, tap0);
   DASAC_CHECK_LAUNCH("wgrad_reduce");
+  return DASAC_OK;
+}
+
+// `batch` weight gradients over plain matrices as ONE launch (conv_wgrad_batched above; include/dasac_hip.h).  The pixel splits
+// are chosen over all batch * m_tiles * k_tiles tiles; 0 = the launch does not take this shape.
+extern "C" int dasac_conv_wgrad_batched_splits(int batch, int M, int C, int T) {
+  if (batch < 1 || batch > 65535 || M <= 0 || C <= 0 || T <= 0 || M % 128 || C % 128 || T % 4) return 0;
+  if ((int64_t)M * T * 4 >= (1ll << 31) || (int64_t)C * T * 4 >= (1ll << 31)) return 0;   // an entry's window, the scalar row offsets
+  if ((int64_t)batch * M * C * 4 > kMaxTensorBytes) return 0;                               // one split's slabs: at most 2^16 tiles
+  const int tiles = batch * (M / 128) * (C / 128);
+  constexpr int kMinPix = 256;                                 // at least 8 K-steps per split, at most 64 splits: as wgrad_splits
+  int max_splits = (T + kMinPix - 1) / kMinPix;
+  if (max_splits > 64) max_splits = 64;
+  const int splits = fill_rounds(tiles, max_splits, kNumCu * 3);
+  return (int64_t)splits * batch * M * C * 4 <= kMaxTensorBytes ? splits : 0;
+}
+
+extern "C" size_t dasac_conv_wgrad_batched_workspace(int batch, int M, int C, int T) {
+  const int splits = dasac_conv_wgrad_batched_splits(batch, M, C, T);
+  return (size_t)splits * ((size_t)batch * M * C + M) * sizeof(float);          // slabs + per-split row sums
+}
+
+extern "C" int dasac_conv_wgrad_batched(const float* a, const float* b, int batch, int M, int C, int T, int64_t a_stride,
+                                        int64_t b_stride, int sum_entry, void* workspace, size_t ws_bytes, dasac_stream_t stream) {
+  DASAC_REQUIRE(a && b && workspace, "conv_wgrad_batched: null pointer");
+  DASAC_REQUIRE(sum_entry >= 0 && sum_entry < batch, "conv_wgrad_batched: sum_entry %d outside 0..batch-1", sum_entry);
+  const int splits = dasac_conv_wgrad_batched_splits(batch, M, C, T);
+  DASAC_REQUIRE(splits > 0, "conv_wgrad_batched: needs batch in 1..65535, M and C multiples of 128, T a multiple of 4, entries below 2 GiB "
+                            "and slabs inside the 4 GiB window (batch %d, M %d, C %d, T %d)", batch, M, C, T);
+  DASAC_REQUIRE(a_stride >= (int64_t)M * T && b_stride >= (int64_t)C * T && a_stride % 4 == 0 && b_stride % 4 == 0,
+                "conv_wgrad_batched: a per-batch stride is smaller than one entry or not a multiple of 4 elements");
+  if (ws_bytes < dasac_conv_wgrad_batched_workspace(batch, M, C, T)) return fail(DASAC_EWORKSPACE, "conv_wgrad_batched: workspace too small");
+  int per = (T + splits - 1) / splits;
+  per = (per + kWgPix - 1) / kWgPix * kWgPix;
+  float* P = reinterpret_cast<float*>(workspace);
+  float* Psum = P + (size_t)splits * batch * M * C;
+  const WgradBatch w{M, C, T, M / 128, C / 128, splits, per, sum_entry, a_stride, b_stride};
+  const int grid = (w.m_tiles * w.k_tiles * splits + kNumXcd - 1) / kNumXcd * kNumXcd;
+  hipLaunchKernelGGL(conv_wgrad_batched, dim3(grid, batch), dim3(kThreads), 0, as_stream(stream), a, b, P, Psum, w);
+  DASAC_CHECK_LAUNCH("conv_wgrad_batched");
   return DASAC_OK;
 }
 

@@ -6,6 +6,12 @@
 //   16 point GEMMs     Y[pt][m][tile] = sum_c U[pt][m][c] * V[pt][c][tile]          (dasac_conv_gemm, 1x1, H = 1, W = tiles)
 //   output transform   out[n][m][y][x] = epi((A^T Y A)[ey][ex]) -- shift, ReLU, ReLU bits recorded or consumed
 //
+// and the weight gradient as the exact adjoint, dW = G^T [sum over tiles (A dY A^T) (.) (B^T d B)] G:
+//
+//   grad transform     dM[pt][m][tile] = (A dY A^T)[pt] of every tile's 2x2 output pixels
+//   16 contractions    P[split][pt][m][c] = sum over the split's tiles of dM[pt][m][t] * V[pt][c][t]   (dasac_conv_wgrad_batched, ONE launch)
+//   finish             dW[m][c] = scale[m] * G^T (sum_split P) G, the frozen BN's dot rows and sum of dz
+//
 // 2.25 x fewer multiplies than the direct contraction; the price is two passes over [16][C][tiles] tensors.  No new matrix kernel.
 // Index arithmetic lives in winograd_index.hpp and is walked on the host by tools/winograd_index_check.cpp.  Every global access
 // goes through a buffer descriptor of the tensor's exact extent with the whole offset in the per-lane operand (the scalar
@@ -149,6 +155,107 @@ __global__ __launch_bounds__(kBlock) void output_transform(const float* __restri
   }
 }
 
+// ---- weight gradient: transform of dY ----------------------------------------------------------------------------------------
+// The adjoint of the output transform.  grid (ceil(T / 256), M): one thread per (channel, tile), lanes along tiles, tiles numbered as
+// input_transform numbers them.  dM = A dY A^T of the tile's 2x2 output pixels, A = [[1,0],[1,1],[1,-1],[0,-1]]; output (ey, ex)
+// is tap (ey + 1, ex + 1) of the tile's patch, so a pixel of a tile that hangs over the map edge takes patch_offset's zero.
+__global__ __launch_bounds__(kBlock) void grad_transform(const float* __restrict__ dY, float* __restrict__ dM, Geom g, int M,
+                                                          unsigned y_bytes, unsigned m_bytes) {
+  const int tile = blockIdx.x * kBlock + threadIdx.x;
+  if (tile >= g.T) return;
+  const int m = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t ry = make_rsrc(dY, y_bytes), rm = make_rsrc(dM, m_bytes);
+  int n, y0, x0;
+  tile_origin(g, tile, n, y0, x0);
+  float d[2][2];
+#pragma unroll
+  for (int ey = 0; ey < 2; ++ey)
+#pragma unroll
+    for (int ex = 0; ex < 2; ++ex) d[ey][ex] = ld(ry, patch_offset(g, M, n, m, y0, x0, ey + 1, ex + 1));
+  float t[4][2];                                           // A dY
+#pragma unroll
+  for (int ex = 0; ex < 2; ++ex) {
+    t[0][ex] = d[0][ex];
+    t[1][ex] = d[0][ex] + d[1][ex];
+    t[2][ex] = d[0][ex] - d[1][ex];
+    t[3][ex] = -d[1][ex];
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const float v[4] = {t[a][0], t[a][0] + t[a][1], t[a][0] - t[a][1], -t[a][1]};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) st(rm, point_offset(g, M, a * 4 + b, m, tile), v[b]);
+  }
+}
+
+// ---- weight gradient: finish -------------------------------------------------------------------------------------------------
+// P [splits][16][M][C] (the batched point contraction's slabs), Psum [splits][M] (channel sums of point (1,1) of dM = sum of dz)
+// -> dW[co][ci][3][3] = scale[co] * (G^T (sum_s P[s]) G), dot[blockIdx.x][co] = this block's part of sum W * (unscaled gradient),
+// sum_dz[co] = sum_s Psum[s][co]: dot and sum_dz exactly as dasac_conv_wgrad_finish leaves them.  grid (C / 64, M), 256 threads =
+// 64 input channels x 4 split lanes; a thread adds the splits s = lane, lane + 4, ... of its channel's 16 points, the four lanes
+// meet in LDS in a fixed order, and the block writes its 64 x 9 gradients as one contiguous run of dW.
+__global__ __launch_bounds__(kBlock) void wgrad_finish(const float* __restrict__ P, const float* __restrict__ Psum, int splits, int M,
+                                                        int C, const float* __restrict__ Wt, const float* __restrict__ scale,
+                                                        float* __restrict__ dW, float* __restrict__ dot, float* __restrict__ sum_dz,
+                                                        unsigned p_bytes, unsigned w_bytes) {
+  const int co = blockIdx.y, ci0 = blockIdx.x * 64;
+  const int tx = threadIdx.x, c = tx & 63, q = tx >> 6;
+  const __amdgpu_buffer_rsrc_t rp = make_rsrc(P, p_bytes), rw = make_rsrc(Wt, w_bytes), rd = make_rsrc(dW, w_bytes);
+  if (sum_dz && blockIdx.x == 0 && q == 0) {                 // one wave: the splits' channel sums in parallel
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(Psum, (unsigned)(splits * M) * 4u);
+    float sv = 0.f;
+    for (int s = c; s < splits; s += 64) sv += ld(rs, (unsigned)(s * M + co) * 4u);
+    sv = wave_sum(sv);
+    if (c == 0) st(make_rsrc(sum_dz, (unsigned)M * 4u), (unsigned)co * 4u, sv);
+  }
+  __shared__ float red[4][16][64];
+  __shared__ float grad[64 * 9];
+  float acc[16];
+#pragma unroll
+  for (int pt = 0; pt < 16; ++pt) acc[pt] = 0.f;
+  const unsigned point = (unsigned)(M * C), slab = 16u * point;
+  const unsigned e0 = (unsigned)(co * C + ci0 + c);
+  for (int s = q; s < splits; s += 4)
+#pragma unroll
+    for (int pt = 0; pt < 16; ++pt) acc[pt] += ld(rp, ((unsigned)s * slab + (unsigned)pt * point + e0) * 4u);
+#pragma unroll
+  for (int pt = 0; pt < 16; ++pt) red[q][pt][c] = acc[pt];
+  __syncthreads();
+  if (q == 0) {
+    float p[4][4];
+#pragma unroll
+    for (int pt = 0; pt < 16; ++pt) p[pt >> 2][pt & 3] = (red[0][pt][c] + red[1][pt][c]) + (red[2][pt][c] + red[3][pt][c]);
+    float r[3][4];                                         // G^T P
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      r[0][b] = p[0][b] + 0.5f * (p[1][b] + p[2][b]);
+      r[1][b] = 0.5f * (p[1][b] - p[2][b]);
+      r[2][b] = 0.5f * (p[1][b] + p[2][b]) + p[3][b];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      grad[c * 9 + a * 3 + 0] = r[a][0] + 0.5f * (r[a][1] + r[a][2]);
+      grad[c * 9 + a * 3 + 1] = 0.5f * (r[a][1] - r[a][2]);
+      grad[c * 9 + a * 3 + 2] = 0.5f * (r[a][1] + r[a][2]) + r[a][3];
+    }
+  }
+  __syncthreads();
+  const float sc = scale ? ld(make_rsrc(scale, (unsigned)M * 4u), (unsigned)co * 4u) : 1.f;
+  float part = 0.f;
+  for (int e = tx; e < 64 * 9; e += kBlock) {
+    const unsigned off = ((unsigned)(co * C + ci0) * 9u + (unsigned)e) * 4u;
+    if (dot) part += grad[e] * ld(rw, off);
+    st(rd, off, grad[e] * sc);
+  }
+  if (dot) {
+    __shared__ float redd[4];
+    part = wave_sum(part);
+    if (c == 0) redd[q] = part;
+    __syncthreads();
+    if (tx == 0) st(make_rsrc(dot, (unsigned)((C / 64) * M) * 4u), (unsigned)(blockIdx.x * M + co) * 4u, (redd[0] + redd[1]) + (redd[2] + redd[3]));
+  }
+}
+
 }  // namespace wino
 }  // namespace dasac
 
@@ -229,5 +336,38 @@ extern "C" int dasac_winograd_output(const float* y, size_t y_bytes, int Nb, int
     hipLaunchKernelGGL(wino::output_transform<0>, grid, block, 0, s, y, out, g, M, shift, relu, mask_bits, relu_bits_out, w32,
                        (unsigned)need, out_bytes, bits_bytes);
   DASAC_CHECK_LAUNCH("winograd output_transform");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd_grad_input(const float* dz, int Nb, int M, int H, int W, int dilation, float* dm, size_t dm_bytes,
+                                         dasac_stream_t stream) {
+  DASAC_REQUIRE(dz && dm, "winograd_grad_input: null pointer");
+  Geom g;
+  const int rc = wino_geom(g, "winograd_grad_input", Nb, M, M, H, W, dilation);
+  if (rc) return rc;
+  DASAC_REQUIRE(M <= 65535, "winograd_grad_input: more than 65535 channels");
+  const size_t need = (size_t)16 * M * g.T * 4;
+  if (dm_bytes < need) return fail(DASAC_EWORKSPACE, "winograd_grad_input: workspace too small (%zu < %zu)", dm_bytes, need);
+  hipLaunchKernelGGL(wino::grad_transform, dim3((g.T + wino::kBlock - 1) / wino::kBlock, M), dim3(wino::kBlock), 0, as_stream(stream), dz,
+                     dm, g, M, (unsigned)((int64_t)Nb * M * H * W * 4), (unsigned)need);
+  DASAC_CHECK_LAUNCH("winograd grad_transform");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd_wgrad_finish(const void* workspace, size_t ws_bytes, int M, int C, int T, const float* w,
+                                           const float* scale, float* dw, float* dot, float* sum_dz, dasac_stream_t stream) {
+  DASAC_REQUIRE(workspace && w && dw, "winograd_wgrad_finish: null pointer");
+  DASAC_REQUIRE(M > 0 && M <= 65535 && C > 0 && C % 64 == 0, "winograd_wgrad_finish: needs 1..65535 output channels and a multiple of 64 input channels");
+  const int splits = dasac_conv_wgrad_batched_splits(16, M, C, T);
+  DASAC_REQUIRE(splits > 0, "winograd_wgrad_finish: the batched weight-gradient launch does not take this shape");
+  const size_t need = dasac_conv_wgrad_batched_workspace(16, M, C, T);
+  if (ws_bytes < need) return fail(DASAC_EWORKSPACE, "winograd_wgrad_finish: workspace too small (%zu < %zu)", ws_bytes, need);
+  const int64_t p_elems = (int64_t)splits * 16 * M * C;
+  DASAC_REQUIRE(p_elems * 4 <= wino::kMaxBytes && (int64_t)M * C * 9 * 4 <= wino::kMaxBytes,
+                "winograd_wgrad_finish: a tensor exceeds the 4 GiB buffer-descriptor window");
+  const float* P = reinterpret_cast<const float*>(workspace);
+  hipLaunchKernelGGL(wino::wgrad_finish, dim3(C / 64, M), dim3(wino::kBlock), 0, as_stream(stream), P, P + p_elems, splits, M, C, w, scale,
+                     dw, dot, sum_dz, (unsigned)(p_elems * 4), (unsigned)((int64_t)M * C * 9 * 4));
+  DASAC_CHECK_LAUNCH("winograd wgrad_finish");
   return DASAC_OK;
 }

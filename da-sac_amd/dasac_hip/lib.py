@@ -83,6 +83,11 @@ PROTOTYPES = {
     "dasac_winograd_filter": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "dasac_winograd_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "dasac_winograd_output": (_i, [_p, _sz, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "dasac_winograd_grad_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "dasac_conv_wgrad_batched_splits": (_i, [_i, _i, _i, _i]),
+    "dasac_conv_wgrad_batched_workspace": (_sz, [_i, _i, _i, _i]),
+    "dasac_conv_wgrad_batched": (_i, [_p, _p, _i, _i, _i, _i, _l, _l, _i, _p, _sz, _p]),
+    "dasac_winograd_wgrad_finish": (_i, [_p, _sz, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "dasac_conv_pack_expanded":(_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dasac_tap_gather": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "dasac_tap_scatter": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),

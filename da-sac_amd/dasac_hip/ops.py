@@ -317,8 +317,9 @@ def conv_dgrad(spec, dz, weights, in_hw, scale=None, res=None, mask=None, table=
 # ----------------------------------------------------------------------------------------------
 # Winograd F(2x2,3x3) for the wide dilated 3x3 convolutions (include/dasac_hip.h: dasac_winograd_*)
 # ----------------------------------------------------------------------------------------------
-# Algorithm of the forward / data-gradient GEMMs of an eligible convolution:
-#   "auto"    Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2), direct elsewhere;
+# Algorithm of the forward / data-gradient / weight-gradient GEMMs of an eligible convolution:
+#   "auto"    Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2) and, for the weight gradient,
+#             where `winograd_wgrad_routed` does (layer4's and layer3's conv2), direct elsewhere;
 #   "direct"  the direct implicit GEMM everywhere.
 ALGORITHM = "auto"
 # Layer3's 256 -> 256 measures faster through the batched Winograd path too (0.69 -> 0.59 ms per conv, 11.6 ms per cfg-3 step) but stays
@@ -428,6 +429,59 @@ def winograd_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, b
         for pt in range(16):
             conv_gemm(v[pt].view(1, C, 1, T), u[pt], table, y[pt].view(1, M, 1, T), (1, T), 1, M, C, schedule=gemm_schedule)
     return winograd_output(y, out, dilation, shift, relu, mask_bits, bits_out)
+
+
+# The weight gradient of the same convolutions has its own threshold: it is routed where it measured faster on its own, whatever the
+# forward and the data gradient of the layer do -- layer4's 512 -> 512 (2.80 -> 1.64 ms per conv) AND layer3's 256 -> 256 (0.714 ->
+# 0.520 ms; profiles/winograd_wgrad_ab.txt): no test counts conv_wgrad launches.
+WINOGRAD_WGRAD_MIN_CHANNEL_PRODUCT = 256 * 256
+
+
+def winograd_wgrad_routed(spec, Nb, H, W):
+    """The engine's rule for the weight gradient: eligible (`winograd_ok`: one 3x3 branch, fp32, ...), wide enough to pay, the
+    transformed tensors inside the 4 GiB window and a shape the batched point contraction takes (channel counts multiples of
+    128, a tile count that is a multiple of 4: dasac_conv_wgrad_batched)."""
+    if ALGORITHM != "auto" or not winograd_ok(spec) or spec.cin * spec.cout < WINOGRAD_WGRAD_MIN_CHANNEL_PRODUCT:
+        return False
+    lib = L.load()
+    T = lib.dasac_winograd_tiles(Nb, H, W, spec.branches[0][2])
+    return T > 0 and 64 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES \
+        and lib.dasac_conv_wgrad_batched_splits(16, spec.cout, spec.cin, T) > 0
+
+
+def winograd_wgrad(spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=None):
+    """dW [Cout,Cin,3,3] of an eligible 3x3 convolution as G^T [sum over tiles (A dY A^T) (.) (B^T x B)] G: the input transform of
+    x, its adjoint on dz, ONE batched launch of the 16 point contractions over pixel splits, and a finish that adds the splits in a
+    fixed order, transforms back and multiplies by scale[co].  `dot` [dot_rows(spec), Cout], `sum_dz` [Cout] and `out` are those
+    of `conv_wgrad`.  The two transformed tensors and the slabs live in the stream's scratch buffer."""
+    lib = L.load()
+    L.require_gpu(dz, x, weight, scale, dot, sum_dz)
+    Nb, C, H, W = x.shape
+    M, d = dz.shape[1], int(spec.branches[0][2])
+    assert winograd_ok(spec) and (C, M) == (spec.cin, spec.cout) and tuple(dz.shape) == (Nb, M, H, W) and x.is_contiguous()
+    assert dot is None or (tuple(dot.shape) == (dot_rows(spec), M) and dot.is_contiguous())
+    T = lib.dasac_winograd_tiles(Nb, H, W, d)
+    slab_bytes = lib.dasac_conv_wgrad_batched_workspace(16, M, C, T) if T > 0 else 0
+    if slab_bytes == 0 or 64 * max(C, M) * T > _MAX_TENSOR_BYTES:
+        raise L.DasacError("winograd_wgrad: {} x {} channels over {} tiles has no batched point contraction".format(M, C, T))
+    v_elems, m_elems = 16 * C * T, 16 * M * T
+    ws = L.workspace(4 * (v_elems + m_elems) + slab_bytes, x.device)
+    v, dm, slabs = ws[:4 * v_elems], ws[4 * v_elems:4 * (v_elems + m_elems)], ws[4 * (v_elems + m_elems):]
+    dz = _c(dz)
+    with PROFILE.span("winograd_wgrad_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
+        L.check(lib.dasac_winograd_input(x.data_ptr(), Nb, C, H, W, d, v.data_ptr(), v.numel(), L.stream_ptr()), "dasac_winograd_input")
+    with PROFILE.span("winograd_wgrad_grad", 0.0, None, 4.0 * (dz.numel() + m_elems)):
+        L.check(lib.dasac_winograd_grad_input(dz.data_ptr(), Nb, M, H, W, d, dm.data_ptr(), dm.numel(), L.stream_ptr()),
+                "dasac_winograd_grad_input")
+    with PROFILE.span("winograd_wgrad_gemm", 2.0 * 16 * M * C * T, (M, C, T, 1, 1, False, False), 4.0 * (v_elems + m_elems + 16 * M * C)):
+        # entry 5 = point (1,1): its row sums are the channel sums of dz
+        L.check(lib.dasac_conv_wgrad_batched(dm.data_ptr(), v.data_ptr(), 16, M, C, T, M * T, C * T, 5, slabs.data_ptr(), slabs.numel(),
+                                             L.stream_ptr()), "dasac_conv_wgrad_batched")
+    dw = _dest(out, weight)
+    with PROFILE.span("winograd_wgrad_finish", 0.0, None, float(slab_bytes) + 8.0 * weight.numel()):
+        L.check(lib.dasac_winograd_wgrad_finish(slabs.data_ptr(), slabs.numel(), M, C, T, _c(weight).data_ptr(), L.ptr(scale), dw.data_ptr(),
+                                                L.ptr(dot), L.ptr(sum_dz), L.stream_ptr()), "dasac_winograd_wgrad_finish")
+    return dw
 
 
 def dot_rows(spec):

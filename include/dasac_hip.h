@@ -215,6 +215,34 @@ int dasac_winograd_input(const float* x, int Nb, int C, int H, int W, int dilati
                          dasac_stream_t stream);
 int dasac_winograd_output(const float* y, size_t y_bytes, int Nb, int M, int H, int W, int dilation, const float* shift,
                           int relu, const uint32_t* mask_bits, uint32_t* relu_bits_out, float* out, dasac_stream_t stream);
+/* Weight gradient of the same convolutions in the same form, the exact adjoint of the forward path:
+ * dW = G^T [ sum over tiles of (A dY A^T) (.) (B^T x B) ] G, 2.25 x fewer multiplies than dasac_conv_wgrad.
+ *   dasac_winograd_input        v [16][C][T] = B^T d B of x, as in the forward pass (recomputed: nothing is kept from it)
+ *   dasac_winograd_grad_input   dm [16][M][T] = (A dY A^T)[pt] of every tile's 2x2 output pixels of dz [Nb,M,H,W], A = [[1,0],[1,1],
+ *                               [1,-1],[0,-1]], tiles numbered as dasac_winograd_input numbers them; a pixel of a tile that hangs
+ *                               over the map edge counts as zero.  dm_bytes >= 16*M*T*4.
+ *   dasac_conv_wgrad_batched    `batch` weight gradients over plain row-major matrices as ONE launch (grid y = batch entry):
+ *                               P[split][b][m][c] = sum over the split's t of a[b][m][t] * b[b][c][t], entries a_stride / b_stride
+ *                               ELEMENTS apart, slabs in `workspace` (dasac_conv_wgrad_batched_workspace bytes), followed by
+ *                               Psum[split][m] = the split's row sums of entry `sum_entry` of a.  The pixel splits
+ *                               (dasac_conv_wgrad_batched_splits; 0 = shape not taken) are chosen over all batch * M/128 * C/128
+ *                               tiles.  Fixed summation order, no atomics: the bits repeat from run to run.  Needs batch in
+ *                               1..65535, M and C multiples of 128, T a multiple of 4, strides >= one entry's extent (M*T, C*T)
+ *                               and multiples of 4 elements, an entry below 2 GiB and the slabs inside the 4 GiB window; anything
+ *                               else is DASAC_EINVAL.  The Winograd weight gradient calls it with a = dm, b = v, batch = 16 and
+ *                               sum_entry = 5: point (1,1) of A dY A^T is the tile's pixel sum, so its row sums are sum dz.
+ *   dasac_winograd_wgrad_finish adds the splits in a fixed order, applies G^T (.) G and writes dw[co][ci][3][3] = scale[co] * gradient
+ *                               (scale may be NULL); dot (may be NULL) [C/64][M] and sum_dz (may be NULL) [M] are what
+ *                               dasac_conv_wgrad_finish leaves there: per block of 64 input channels the partial sum of w * (unscaled
+ *                               gradient), and the sum of dz over batch and pixels.  M = Cout, C = Cin (a multiple of 64). */
+int dasac_winograd_grad_input(const float* dz, int Nb, int M, int H, int W, int dilation, float* dm, size_t dm_bytes,
+                              dasac_stream_t stream);
+int dasac_conv_wgrad_batched_splits(int batch, int M, int C, int T);
+size_t dasac_conv_wgrad_batched_workspace(int batch, int M, int C, int T);
+int dasac_conv_wgrad_batched(const float* a, const float* b, int batch, int M, int C, int T, int64_t a_stride, int64_t b_stride,
+                             int sum_entry, void* workspace, size_t ws_bytes, dasac_stream_t stream);
+int dasac_winograd_wgrad_finish(const void* workspace, size_t ws_bytes, int M, int C, int T, const float* w, const float* scale,
+                                float* dw, float* dot, float* sum_dz, dasac_stream_t stream);
 
 /* Tap-expanded evaluation of few-output-channel, many-tap convolutions -- the ASPP classifiers
  * (deeplabv2.py:101-116): Y[(tap,co)] = 1x1 GEMM over taps*Cp channels (dasac_conv_gemm with weights

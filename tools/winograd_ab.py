@@ -1,11 +1,12 @@
 """A/B of ONE layer4 conv2 (512 -> 512, 3x3, dilation 4, 8 crops of 97 x 97; with --channels 256 --dilation 2 one of layer3): the
-direct implicit GEMM against the Winograd F(2x2,3x3) path, forward (shift + ReLU + recorded bits) and data gradient (masked with
-recorded bits), as the engine issues them.
+direct implicit GEMM against the Winograd F(2x2,3x3) path, forward (shift + ReLU + recorded bits), data gradient (masked with
+recorded bits) and weight gradient (scaled, with the frozen BN's dot rows and channel sums), as the engine issues them.
 
     python tools/winograd_ab.py [--reps 3] [--iters 10] [--direct-only] [--gemm-schedule -1 1 2]
 
 Per repetition: `iters` back-to-back evaluations between one HIP event pair -> ms per conv, summing every launch that replaces
-the direct one (input transform + the 16 point GEMMs, as one batched launch or as 16 + output transform).  A second pass splits
+the direct one (input transform + the 16 point GEMMs, as one batched launch or as 16 + output transform; weight gradient: both
+transforms + the batched point contraction + finish, against conv_wgrad + its finish).  A second pass splits
 the Winograd time per kernel with an event pair per launch (ops.PROFILE).  With DASAC_LIB naming an older build of the library
 the figures are that build's (the A/B against the parent commit on the same box): --direct-only for its direct GEMM,
 --gemm-schedule 2 for the 16-launch form an older build has."""
@@ -63,9 +64,13 @@ def main():
     of, ot = ops.gemm_order(spec, False), ops.gemm_order(spec, True)
     tab_f, tab_t = ops.conv_table(spec, S, S, False, dev, of), ops.conv_table(spec, S, S, True, dev, ot)
     pk_f, pk_t = ops.conv_pack(spec, [w], False, scale, order=of), ops.conv_pack(spec, [w], True, scale, order=ot)
+    # weight gradient as the engine issues it behind a frozen BN: scaled, with the partial dot rows and the channel sums of dz
+    tab_w = ops.conv_table(spec, S, S, False, dev)
+    dw, dot, sums = torch.empty_like(w), torch.empty(ops.dot_rows(spec), C, device=dev), torch.empty(C, device=dev)
     legs = {
         "forward direct": lambda: ops.conv_gemm(x, pk_f, tab_f, out, (S, S), 1, C, spec.K, 1, shift, None, None, True, bits_out=bits),
         "dgrad   direct": lambda: ops.conv_gemm(dz, pk_t, tab_t, dx, (S, S), 1, C, spec.Kt, 1, None, None, mask, False),
+        "wgrad   direct": lambda: ops.conv_wgrad(spec, dz, x, [w], scale=scale, dot=dot, table=tab_w, sum_dz=sums, outs=[dw]),
     }
     if not args.direct_only:
         u_f, u_t = ops.winograd_filter(spec, w, False, scale), ops.winograd_filter(spec, w, True, scale)
@@ -73,6 +78,8 @@ def main():
             sfx = "" if len(scheds) == 1 else " (--gemm-schedule {})".format(v)
             legs["forward winograd" + sfx] = lambda sched=sched: ops.winograd_conv(x, u_f, out, d, shift, True, bits_out=bits, gemm_schedule=sched)
             legs["dgrad   winograd" + sfx] = lambda sched=sched: ops.winograd_conv(dz, u_t, dx, d, mask_bits=mask, gemm_schedule=sched)
+        if hasattr(L.load(), "dasac_conv_wgrad_batched"):      # absent from an older build named by DASAC_LIB
+            legs["wgrad   winograd"] = lambda: ops.winograd_wgrad(spec, dz, x, w, scale=scale, dot=dot, sum_dz=sums, out=dw)
         legs["filter transform (per weight update, forward + dgrad)"] = lambda: (ops.winograd_filter(spec, w, False, scale, out=u_f),
                                                                                  ops.winograd_filter(spec, w, True, scale, out=u_t))
     print("library: {}   shape: {} x {} -> {} x {} x {}, dilation {}   {} iterations per repetition".format(
