@@ -681,6 +681,157 @@ __global__ __launch_bounds__(256) void grad_norm_finish(const double* __restrict
   }
 }
 
+// ---- per-tensor gradient health table: one more multi-tensor pass over the update's own table ---------
+// Columns of a row (fp64; counts and indices are exact integers below 2^53), d = g2 + g as in grad_sq_chunks:
+//   0 g_sumsq            sum d^2 over FINITE d              4 g_zeros   number of d == 0 (either sign)
+//   1 g_maxabs           max |d| over finite d, 0 if none   5 p_sumsq   sum p^2 plainly (Inf / NaN show)
+//   2 g_nonfinite        number of d that are Inf or NaN    6 p_maxabs  max |p| over finite p
+//   3 g_first_nonfinite  1 + flat index of the first, or 0  7 s_sumsq   sum state^2 plainly, 0 without a state
+constexpr int kStatCols = 8;
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// elements i .. i+3 of a tensor of n: one dwordx4 load where `vec` (whole chunk, 16-byte aligned pointer), four guarded scalar
+// loads otherwise (0 beyond the end)
+__device__ __forceinline__ f32x4 chunk_load4(const float* __restrict__ x, int64_t i, int64_t n, bool vec) {
+  if (vec) return *reinterpret_cast<const f32x4*>(x + i);
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = i + e < n ? x[i + e] : 0.f;
+  return v;
+}
+
+// One partial row per (tensor, chunk), no atomics.  Rows as grad_sq_chunks reads them, plus p at byte 0 and the state pointer
+// (momentum_buffer / exp_avg) at byte 24; either may be null: zeros in its columns.  first_bit (the SGD table): bit 32 of `group`
+// (the 8 bytes after n) marks a tensor that takes its first step -- its momentum buffer is uninitialised memory and is NOT read.
+// Thread t owns elements (j*256 + t)*4 + e on the vector and on the scalar path, each input takes the path its own pointer
+// allows, and the per-thread sums run in the same order on both: the table does not depend on where a tensor lies.
+__global__ __launch_bounds__(256) void tensor_stats_chunks(const char* __restrict__ rows, int row_bytes, int n_off, int first_bit,
+                                                           const int2* __restrict__ chunks, double* __restrict__ partial) {
+  const int2 ch = chunks[blockIdx.x];
+  const char* row = rows + (size_t)ch.x * row_bytes;
+  const float* p = *reinterpret_cast<const float* const*>(row);
+  const float* g = *reinterpret_cast<const float* const*>(row + 8);
+  const float* g2 = *reinterpret_cast<const float* const*>(row + 16);
+  const float* st = *reinterpret_cast<const float* const*>(row + 24);
+  const int64_t n = *reinterpret_cast<const int64_t*>(row + n_off);
+  if (first_bit && ((*reinterpret_cast<const int64_t*>(row + n_off + 8) >> 32) & 1)) st = nullptr;
+  const int64_t base = (int64_t)ch.y * kEmaChunk;
+  const bool whole = base + kEmaChunk <= n;
+  const bool vec_g = whole && (((uintptr_t)g | (uintptr_t)g2) & 15) == 0;
+  const bool vec_p = whole && ((uintptr_t)p & 15) == 0, vec_s = whole && ((uintptr_t)st & 15) == 0;
+  double g_sq = 0, p_sq = 0, s_sq = 0;
+  float g_max = 0.f, p_max = 0.f;
+  int nonfinite = 0, zeros = 0, first = kEmaChunk;      // first: offset inside the chunk, kEmaChunk = none
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int off = (j * 256 + threadIdx.x) * 4;
+    const int64_t i = base + off;
+    f32x4 d = chunk_load4(g, i, n, vec_g);
+    if (g2) {
+      const f32x4 d2 = chunk_load4(g2, i, n, vec_g);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d[e] = d2[e] + d[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (whole || i + e < n) {
+        if (isfinite(d[e])) {
+          g_sq += (double)d[e] * (double)d[e];
+          g_max = fmaxf(g_max, fabsf(d[e]));
+          zeros += d[e] == 0.f;
+        } else {
+          ++nonfinite;
+          first = min(first, off + e);
+        }
+      }
+    }
+    if (p) {      // elements beyond the end load as 0: nothing to guard
+      const f32x4 v = chunk_load4(p, i, n, vec_p);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        p_sq += (double)v[e] * (double)v[e];
+        if (isfinite(v[e])) p_max = fmaxf(p_max, fabsf(v[e]));
+      }
+    }
+    if (st) {
+      const f32x4 v = chunk_load4(st, i, n, vec_s);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s_sq += (double)v[e] * (double)v[e];
+    }
+  }
+  __shared__ double red[4][kStatCols];
+  g_sq = wave_sum(g_sq), p_sq = wave_sum(p_sq), s_sq = wave_sum(s_sq);
+  const double nf = wave_sum((double)nonfinite), zr = wave_sum((double)zeros);
+  g_max = wave_max(g_max), p_max = wave_max(p_max);
+  const double fi = wave_min((double)first);
+  if ((threadIdx.x & 63) == 0) {
+    double* r = red[threadIdx.x >> 6];
+    r[0] = g_sq, r[1] = g_max, r[2] = nf, r[3] = fi, r[4] = zr, r[5] = p_sq, r[6] = p_max, r[7] = s_sq;
+  }
+  __syncthreads();
+  if (threadIdx.x < kStatCols) {      // one column per thread, the four waves in a fixed order
+    const int c = threadIdx.x;
+    const double a = red[0][c], b = red[1][c], e = red[2][c], f = red[3][c];
+    double v;
+    if (c == 1 || c == 6) v = fmax(fmax(a, b), fmax(e, f));
+    else if (c == 3) {
+      v = fmin(fmin(a, b), fmin(e, f));
+      v = v < (double)kEmaChunk ? (double)base + v + 1.0 : 0.0;
+    } else v = (a + b) + (e + f);
+    partial[(size_t)blockIdx.x * kStatCols + c] = v;
+  }
+}
+
+// One block (one wave) per OUTPUT row.  row_of[r] = the row's tensor in this step's table, or -1: eight zeros.  `chunks` is
+// ordered by tensor, so a tensor's partials are one contiguous run (binary search over chunks[].x); lane l combines chunks
+// l, l + 64, ... of the run in ascending order and the lanes meet in the usual butterfly: a fixed order, the same bits every run.
+// ctl non-null and ctl->skip set: the row also goes to `captured`, and block 0 notes *skipped -- which grad_norm_finish has just
+// incremented on the same stream -- in captured_at.
+__global__ __launch_bounds__(64) void tensor_stats_finish(const int2* __restrict__ chunks, int n_chunks, int n_tensors,
+                                                          const int32_t* __restrict__ row_of, const double* __restrict__ partial,
+                                                          double* __restrict__ table, const GradCtl* __restrict__ ctl,
+                                                          double* __restrict__ captured, int64_t* __restrict__ captured_at,
+                                                          const int64_t* __restrict__ skipped) {
+  const int t = row_of[blockIdx.x];
+  double sum[5] = {0, 0, 0, 0, 0}, g_max = 0, p_max = 0, first = 0x1p62;      // sums: columns 0, 2, 4, 5, 7
+  if (t >= 0 && t < n_tensors) {
+    int lo = 0, hi = n_chunks;                       // first chunk whose tensor id is >= t
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (chunks[mid].x < t) lo = mid + 1; else hi = mid;
+    }
+    for (int i = lo + threadIdx.x; i < n_chunks && chunks[i].x == t; i += 64) {
+      const double* r = partial + (size_t)i * kStatCols;
+      sum[0] += r[0], sum[1] += r[2], sum[2] += r[4], sum[3] += r[5], sum[4] += r[7];
+      g_max = fmax(g_max, r[1]), p_max = fmax(p_max, r[6]);
+      if (r[3] > 0) first = fmin(first, r[3]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 5; ++c) sum[c] = wave_sum(sum[c]);
+  g_max = wave_max(g_max), p_max = wave_max(p_max), first = wave_min(first);
+  if (threadIdx.x == 0) {
+    const double out[kStatCols] = {sum[0], g_max, sum[1], first < 0x1p62 ? first : 0.0, sum[2], sum[3], p_max, sum[4]};
+    const bool capture = ctl && ctl->skip;
+#pragma unroll
+    for (int c = 0; c < kStatCols; ++c) {
+      table[(size_t)blockIdx.x * kStatCols + c] = out[c];
+      if (capture) captured[(size_t)blockIdx.x * kStatCols + c] = out[c];
+    }
+    if (capture && blockIdx.x == 0) *captured_at = *skipped;
+  }
+}
+
 // y[n,c,:] = x[n,c,:] * m[n,c]   (Dropout2d with an explicit keep/(1-p) mask, fcn.py:52,56)
 __global__ __launch_bounds__(256) void scale_planes(const float* __restrict__ x, const float* __restrict__ m, int HW,
                                                     float* __restrict__ y, int64_t total) {
@@ -915,6 +1066,43 @@ extern "C" int dasac_grad_norm(const void* tensors, int row_bytes, int n_tensors
   DASAC_CHECK_LAUNCH("grad_sq_chunks");
   hipLaunchKernelGGL(grad_norm_finish, dim3(1), dim3(256), 0, s, sq_chunk, n_chunks, max_norm, reinterpret_cast<GradCtl*>(ctl), skipped);
   DASAC_CHECK_LAUNCH("grad_norm_finish");
+  return DASAC_OK;
+}
+
+extern "C" size_t dasac_tensor_stats_workspace(int n_chunks) {
+  return n_chunks > 0 ? (size_t)n_chunks * kStatCols * sizeof(double) : 0;
+}
+
+extern "C" int dasac_tensor_stats(const void* tensors, int row_bytes, int n_tensors, const int32_t* chunks, int n_chunks,
+                                  const int32_t* row_of, int n_rows, void* workspace, size_t workspace_bytes, double* table,
+                                  const void* ctl, double* captured, int64_t* captured_at, const int64_t* skipped,
+                                  dasac_stream_t stream) {
+  DASAC_REQUIRE(tensors && chunks && row_of && workspace && table && n_tensors > 0 && n_chunks > 0 && n_rows > 0,
+                "tensor_stats: bad arguments");
+  DASAC_REQUIRE(row_bytes == (int)sizeof(SgdTensor) || row_bytes == (int)sizeof(AdamTensor),
+                "tensor_stats: row_bytes names the table, 48 (dasac_sgd_step) or 64 (dasac_adam_step)");
+  DASAC_REQUIRE(((uintptr_t)tensors & 7) == 0 && ((uintptr_t)chunks & 7) == 0 && ((uintptr_t)row_of & 3) == 0 &&
+                    ((uintptr_t)table & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
+                "tensor_stats: misaligned table / chunks / row_of / workspace");
+  DASAC_REQUIRE(workspace_bytes >= dasac_tensor_stats_workspace(n_chunks), "tensor_stats: workspace too small");
+  const int given = (ctl != nullptr) + (captured != nullptr) + (captured_at != nullptr) + (skipped != nullptr);
+  DASAC_REQUIRE(given == 0 || given == 4, "tensor_stats: ctl, captured, captured_at and skipped are all null or all given");
+  DASAC_REQUIRE(((uintptr_t)ctl & 15) == 0 && ((uintptr_t)captured & 7) == 0 && ((uintptr_t)captured_at & 7) == 0 &&
+                    ((uintptr_t)skipped & 7) == 0,
+                "tensor_stats: misaligned control block / captured table / counters");
+  hipStream_t s = as_stream(stream);
+  const bool sgd = row_bytes == (int)sizeof(SgdTensor);
+  const int n_off = sgd ? (int)offsetof(SgdTensor, n) : (int)offsetof(AdamTensor, n);
+  static_assert(offsetof(SgdTensor, p) == 0 && offsetof(AdamTensor, p) == 0 && offsetof(SgdTensor, buf) == 24 && offsetof(AdamTensor, m) == 24 &&
+                    offsetof(SgdTensor, group) == offsetof(SgdTensor, n) + 8 && offsetof(AdamTensor, group) == offsetof(AdamTensor, n) + 8,
+                "tensor_stats_chunks reads p at byte 0, the state pointer at 24 and `group` right after n in either row");
+  double* partial = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(tensor_stats_chunks, dim3(n_chunks), dim3(256), 0, s, reinterpret_cast<const char*>(tensors), row_bytes, n_off,
+                     sgd ? 1 : 0, reinterpret_cast<const int2*>(chunks), partial);
+  DASAC_CHECK_LAUNCH("tensor_stats_chunks");
+  hipLaunchKernelGGL(tensor_stats_finish, dim3(n_rows), dim3(64), 0, s, reinterpret_cast<const int2*>(chunks), n_chunks, n_tensors, row_of,
+                     partial, table, reinterpret_cast<const GradCtl*>(ctl), captured, captured_at, skipped);
+  DASAC_CHECK_LAUNCH("tensor_stats_finish");
   return DASAC_OK;
 }
 

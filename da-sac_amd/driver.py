@@ -5,7 +5,7 @@ DistributedDataParallel wrapper (backend "nccl" == RCCL on ROCm)."""
 import torch
 
 
-def make_optimizer(net, cfg_model, fused=True, max_grad_norm=None, skip_nonfinite=False):
+def make_optimizer(net, cfg_model, fused=True, max_grad_norm=None, skip_nonfinite=False, tensor_stats=False):
     """`BaseTrainer.get_optim` (base_trainer.py:47-73) over the model's four parameter groups (train.py:93-96):
       OPT == "SGD" (the default, configs/*.yaml): SGD(momentum, nesterov=OPT_NESTEROV) -- the fused multi-tensor HIP optimiser
           (same update rule / state layout) for plain momentum or, with fused=False / nesterov, torch.optim.SGD itself;
@@ -17,6 +17,8 @@ def make_optimizer(net, cfg_model, fused=True, max_grad_norm=None, skip_nonfinit
     inside the fused optimisers (dasac_hip/optim.py; `optim.grad_norm` and `optim.skipped_steps` are device tensors).  Either
     one implies fused="all", so that all three cases of the factory have it; ValueError with fused=False or an OPT that has no
     fused class.
+    tensor_stats: the per-tensor gradient health table of the fused optimisers (`track_tensor_stats`: `optim.tensor_stats`,
+    `optim.last_skipped_stats`; read it with `gradient_report` / `skipped_step_report`), under the same rules.
     Every group carries its own lr / weight_decay (basenet.py:102-139), so the keyword defaults below only fill the gaps,
     exactly as in the reference."""
     core = net.module if hasattr(net, "module") else net
@@ -26,10 +28,13 @@ def make_optimizer(net, cfg_model, fused=True, max_grad_norm=None, skip_nonfinit
         print("Optimiser {} not supported".format(opt))
         raise NotImplementedError
     guard = {}
-    if max_grad_norm is not None or skip_nonfinite:
+    if max_grad_norm is not None or skip_nonfinite or tensor_stats:
         if not fused or opt not in ("SGD", "Adam"):
-            raise ValueError("max_grad_norm / skip_nonfinite live in the fused optimisers: not with fused=False or OPT == {!r}".format(opt))
+            raise ValueError("max_grad_norm / skip_nonfinite / tensor_stats live in the fused optimisers: not with fused=False or "
+                             "OPT == {!r}".format(opt))
         fused, guard = "all", dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        if tensor_stats:
+            guard["track_tensor_stats"] = True
     fuse_all = isinstance(fused, str) and fused == "all"
     if opt == "Adam":
         betas = (getattr(cfg_model, "BETA1", 0.5), 0.999)
@@ -150,7 +155,7 @@ def sac_train_iteration(net, optim, src_batch, tgt_batch, group_size, update_tea
     source + target -- on one rank the same sum, bit for bit.  Between the target backward and step(), and after it,
     `.grad` holds the target-pass gradient only: clipping and norm logging therefore happen inside the fused optimisers
     (`make_optimizer(..., max_grad_norm=, skip_nonfinite=)`, `optim.grad_norm`, `optim.measure_grad_norm()`: the norm of
-    source + target, measured on the device); anything else that reads gradients before the step can use `optim.full_grads()`
+    source + target, measured on the device; per tensor: `make_optimizer(..., tensor_stats=True)` and `gradient_report`); anything else that reads gradients before the step can use `optim.full_grads()`
     or pass sum_grads_in_optimizer=False (or another optimiser) for the reference's `.grad` contents.
     Under data parallelism the update is mean_r(src_r) + mean_r(tgt_r) where the reference's DDP reduces
     mean_r(mean(src) + tgt_r): equal in exact arithmetic, one rounding apart in fp32 (not bit-identical) -- for every fused
@@ -586,6 +591,90 @@ def format_confusion(matrix, names):
     lines = [" ".join(["gt \\ pred".ljust(head)] + [n[:width].rjust(width) for n in names])]
     for n, row in zip(names, M.tolist()):
         lines.append(" ".join([n.ljust(head)] + [str(v).rjust(width) for v in row]))
+    return "\n".join(lines)
+
+
+def gradient_report(net, optim, table=None, top=10):
+    """Reading of a gradient health table (`optim.tensor_stats` by default, or e.g. `optim.measure_tensor_stats()`; fp64
+    [n_params, 8], dasac_hip.optim.TENSOR_STATS_COLUMNS, rows in the flattened `param_groups` order).  THE ONE PLACE that copies
+    the table to the host -- a synchronisation: call it when logging, not every step.  Names are those of
+    `net.named_parameters()` (through `.module` if wrapped), lr is each group's.  Returns a plain dict:
+      tensors     one dict per parameter, in table order: name, group, numel, grad_norm, share (of the global squared gradient
+                  norm), g_maxabs, zero_share (g_zeros / numel), weight_norm, update_ratio (lr * ||g|| / ||w||, 0 where ||w|| is 0),
+                  state_norm, nonfinite (count) and first_nonfinite (index tuple in the parameter's shape, or None);
+      groups      the same aggregated per parameter group: group, lr, tensors, numel, grad_norm, share, g_maxabs, zero_share,
+                  weight_norm, update_ratio, state_norm, nonfinite;
+      grad_norm   the global L2 norm over the finite gradient entries;
+      nonfinite   the names of the tensors with non-finite gradient entries;
+      top         the names of the `top` tensors by share, largest first (ties by table order).
+    A parameter without a pending gradient has a row of zeros: it is listed with grad_norm 0 and share 0."""
+    import math
+    import numpy as np
+    core = net.module if hasattr(net, "module") else net
+    names = {p: name for name, p in core.named_parameters()}
+    T = (optim.tensor_stats if table is None else table).detach().cpu().to(torch.float64).numpy()
+    params = [(gi, p) for gi, group in enumerate(optim.param_groups) for p in group["params"]]
+    assert T.shape == (len(params), 8), (T.shape, len(params))
+    total_sq = float(T[:, 0].sum())
+    share = lambda sq: sq / total_sq if total_sq > 0 else 0.0
+    ratio = lambda lr, g, w: lr * g / w if w > 0 else 0.0
+    tensors = []
+    for i, ((gi, p), row) in enumerate(zip(params, T.tolist())):
+        g_norm, w_norm, lr = math.sqrt(row[0]), math.sqrt(row[5]), float(optim.param_groups[gi]["lr"])
+        first = tuple(int(v) for v in np.unravel_index(int(row[3]) - 1, tuple(p.shape))) if row[3] > 0 else None
+        tensors.append(dict(name=names.get(p, "param{}".format(i)), group=gi, numel=p.numel(), grad_norm=g_norm, share=share(row[0]),
+                            g_maxabs=row[1], zero_share=row[4] / max(p.numel(), 1), weight_norm=w_norm,
+                            update_ratio=ratio(lr, g_norm, w_norm), state_norm=math.sqrt(row[7]), nonfinite=int(row[2]),
+                            first_nonfinite=first))
+    groups = []
+    for gi, group in enumerate(optim.param_groups):
+        rows = T[[i for i, (g, _) in enumerate(params) if g == gi]].reshape(-1, 8)
+        numel = sum(p.numel() for p in group["params"])
+        g_norm, w_norm = math.sqrt(float(rows[:, 0].sum())), math.sqrt(float(rows[:, 5].sum()))
+        groups.append(dict(group=gi, lr=float(group["lr"]), tensors=len(group["params"]), numel=numel, grad_norm=g_norm,
+                           share=share(float(rows[:, 0].sum())), g_maxabs=float(rows[:, 1].max()) if len(rows) else 0.0,
+                           zero_share=float(rows[:, 4].sum()) / max(numel, 1), weight_norm=w_norm,
+                           update_ratio=ratio(float(group["lr"]), g_norm, w_norm), state_norm=math.sqrt(float(rows[:, 7].sum())),
+                           nonfinite=int(rows[:, 2].sum())))
+    order = sorted(range(len(tensors)), key=lambda i: (-tensors[i]["share"], i))
+    return dict(tensors=tensors, groups=groups, grad_norm=math.sqrt(total_sq), nonfinite=[t["name"] for t in tensors if t["nonfinite"]],
+                top=[tensors[i]["name"] for i in order[:top]])
+
+
+def skipped_step_report(net, optim, top=10):
+    """`gradient_report` over `optim.last_skipped_stats` -- the table of the last step that `skip_nonfinite` skipped -- plus
+    `captured_at`: `optim.skipped_steps` as it stood right after that step (0: no step has been skipped, the table is zeros)."""
+    table, at = optim.last_skipped_stats
+    report = gradient_report(net, optim, table=table, top=top)
+    report["captured_at"] = int(at)
+    return report
+
+
+def format_gradient_report(report, top=10):
+    """Fixed-width text table of a `gradient_report` for the log: the `top` tensors by share of the squared gradient norm, then
+    every tensor with non-finite entries that is not among them, then one line per group and the global norm."""
+    by_share = sorted(range(len(report["tensors"])), key=lambda i: (-report["tensors"][i]["share"], i))[:top]
+    shown = by_share + [i for i, t in enumerate(report["tensors"]) if t["nonfinite"] and i not in by_share]
+    rows = [report["tensors"][i] for i in shown]
+    labels = ["group {} (lr {:.3g}, {} tensors)".format(g["group"], g["lr"], g["tensors"]) for g in report["groups"]]
+    head = max([len("tensor")] + [len(t["name"]) for t in rows] + [len(l) for l in labels])
+    cols = ["group", "numel", "|g|", "share", "max|g|", "zeros", "|w|", "lr|g|/|w|", "|state|", "nonfinite", "first"]
+    width = [5, 9, 10, 7, 10, 7, 10, 10, 10, 9, 5]
+
+    def cells(t):
+        return [str(t["group"]), str(t["numel"]), "{:.3e}".format(t["grad_norm"]), "{:.4f}".format(t["share"]), "{:.3e}".format(t["g_maxabs"]),
+                "{:.4f}".format(t["zero_share"]), "{:.3e}".format(t["weight_norm"]), "{:.3e}".format(t["update_ratio"]),
+                "{:.3e}".format(t["state_norm"]), str(t["nonfinite"])]
+    lines = [" ".join(["tensor".ljust(head)] + [c.rjust(w) for c, w in zip(cols, width)])]
+    for t in rows:
+        first = "-" if t["first_nonfinite"] is None else str(t["first_nonfinite"])
+        lines.append(" ".join([t["name"].ljust(head)] + [c.rjust(w) for c, w in zip(cells(t), width)] + [first]))
+    for name, g in zip(labels, report["groups"]):
+        lines.append(" ".join([name.ljust(head)] + [c.rjust(w) for c, w in zip(cells(g), width)] + ["-"]))
+    lines.append("global gradient norm {:.6e}; tensors with non-finite entries: {}".format(
+        report["grad_norm"], ", ".join(report["nonfinite"]) if report["nonfinite"] else "none"))
+    if "captured_at" in report:
+        lines.append("captured at skipped step {}".format(report["captured_at"]))
     return "\n".join(lines)
 
 

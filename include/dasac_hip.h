@@ -441,6 +441,26 @@ int dasac_sgd_nesterov_step_ctl(const void* tensors, int n_tensors, const int32_
 int dasac_adam_step_ctl(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
                         const float* group_wd, int n_groups, double beta1, double beta2, double eps,
                         const void* ctl, int apply_coef, int honour_skip, dasac_stream_t stream);
+/* Per-tensor gradient health table: one more pass over the SAME uploaded table and chunks as dasac_grad_norm (row_bytes 48 or
+ * 64), which also reads p at byte 0 and the state pointer at byte 24 (momentum_buffer / exp_avg); either may be NULL and then
+ * gives zeros in its columns.  table: n_rows x 8 doubles, row r describing tensor row_of[r] of `tensors` (a device int32 array;
+ * -1, a parameter with nothing pending: eight zeros), d = g2 + g being the fp32 sum the update applies:
+ *   0 g_sumsq   sum d^2 over finite d        1 g_maxabs  max |d| over finite d       2 g_nonfinite  number of Inf / NaN d
+ *   3 g_first_nonfinite  1 + flat index of the first non-finite d, 0 if none          4 g_zeros      number of d == 0
+ *   5 p_sumsq   sum p^2 (Inf / NaN show)     6 p_maxabs  max |p| over finite p       7 s_sumsq      sum state^2
+ * One partial row per chunk in `workspace` (dasac_tensor_stats_workspace(n_chunks) bytes), no atomics, partials combined in a
+ * fixed order: the same inputs give the same bits, wherever the tensors lie.
+ * PRECONDITION: `chunks` is ordered by tensor (every tensor's chunks form one contiguous run, tensor ids ascending), as for
+ * dasac_ema_update: the rows are found by binary search.
+ * FIRST STEP: in the 48-byte table a row with bit 32 of `group` set takes its first step (dasac_sgd_step_ctl, first = -1); its
+ * momentum buffer is uninitialised and is not read: s_sumsq = 0.
+ * ctl, captured, captured_at and skipped are all NULL (measure only) or all given: while ctl->skip is set (dasac_grad_norm on
+ * the same stream, before this call) the table is also written to `captured` (n_rows x 8 doubles) and *captured_at = *skipped. */
+size_t dasac_tensor_stats_workspace(int n_chunks);
+int dasac_tensor_stats(const void* tensors, int row_bytes, int n_tensors, const int32_t* chunks, int n_chunks,
+                       const int32_t* row_of, int n_rows, void* workspace, size_t workspace_bytes, double* table,
+                       const void* ctl, double* captured, int64_t* captured_at, const int64_t* skipped,
+                       dasac_stream_t stream);
 int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks,
                      float momentum, int update, double* sq, float* out, dasac_stream_t stream);
 int dasac_scale_planes(const float* x, const float* plane_scale, int64_t planes, int64_t HW,
