@@ -1323,6 +1323,71 @@ def confusion_counts(scores, label_maps, gt, confusion=None, reliability=None, b
     return confusion, reliability
 
 
+CONSISTENCY_MAX_VIEWS, CONSISTENCY_MAX_CLASSES = 8, 32      # DASAC_CONSISTENCY_MAX_VIEWS; the kernel's class limit
+
+
+class ConsistencyTables(tuple):
+    """The three tables of `view_consistency` as views of ONE contiguous int64 buffer (`buffer`: one all-reduce, one D2H copy):
+    agree [C+1,T+1,T+1], flips [C,C], per_view [T,2] (include/dasac_hip.h: dasac_view_consistency)."""
+
+    def __new__(cls, buffer, C, T):
+        C, T = int(C), int(T)
+        if buffer.dtype != torch.int64 or buffer.dim() != 1 or buffer.numel() != consistency_size(C, T) or not buffer.is_contiguous():
+            raise L.DasacError("view_consistency accumulates into a contiguous int64 [{}] buffer for C={}, T={} (got {} {})".format(
+                consistency_size(C, T), C, T, buffer.dtype, tuple(buffer.shape)))
+        a, f = (C + 1) * (T + 1) * (T + 1), C * C
+        self = super().__new__(cls, (buffer[:a].view(C + 1, T + 1, T + 1), buffer[a:a + f].view(C, C), buffer[a + f:].view(T, 2)))
+        self.buffer, self.C, self.T = buffer, C, T
+        return self
+
+    agree = property(lambda self: self[0])
+    flips = property(lambda self: self[1])
+    per_view = property(lambda self: self[2])
+
+    def cpu(self):
+        return ConsistencyTables(self.buffer.cpu(), self.C, self.T)
+
+
+def consistency_size(C, T):
+    return (C + 1) * (T + 1) * (T + 1) + C * C + 2 * T
+
+
+def consistency_tables(C, T, device):
+    """A zeroed buffer for `view_consistency`, as ConsistencyTables."""
+    return ConsistencyTables(torch.zeros(consistency_size(C, T), dtype=torch.int64, device=device), C, T)
+
+
+def view_consistency(aligned, T, tables=None, cover=0.5):
+    """Label-free agreement of the T aligned teacher views of every group in ONE launch (include/dasac_hip.h:
+    dasac_view_consistency).  aligned: fp32 [N*T,C,H,W], view t of group n at n*T + t -- `warp_pool`'s aligned tensor, the
+    `teacher_aligned` of a target step.  A view is covered at a pixel when its class sum is >= `cover`; the consensus is the arg-max of
+    the plain sum over the T views.  Accumulates into `tables` (a ConsistencyTables or its flat int64 buffer; allocated zeroed when
+    None) and returns the ConsistencyTables (agree [C+1,T+1,T+1], flips [C,C], per_view [T,2])."""
+    lib = L.load()
+    L.require_gpu(aligned, tables.buffer if isinstance(tables, ConsistencyTables) else tables)
+    T = int(T)
+    if aligned.dtype != torch.float32 or aligned.dim() != 4:
+        raise L.DasacError("view_consistency takes a float32 [N*T,C,H,W] tensor (got {} {})".format(aligned.dtype, tuple(aligned.shape)))
+    NT, Cn, H, W = aligned.shape
+    if not 1 <= T <= CONSISTENCY_MAX_VIEWS or not 1 <= Cn <= CONSISTENCY_MAX_CLASSES:
+        raise L.DasacError("view_consistency: 1..{} views and 1..{} classes (got T={}, C={})".format(
+            CONSISTENCY_MAX_VIEWS, CONSISTENCY_MAX_CLASSES, T, Cn))
+    if NT == 0 or NT % T:
+        raise L.DasacError("view_consistency: {} views are no whole groups of T={}".format(NT, T))
+    if tables is None:
+        tables = consistency_tables(Cn, T, aligned.device)
+    elif not isinstance(tables, ConsistencyTables):
+        tables = ConsistencyTables(tables, Cn, T)
+    elif (tables.C, tables.T) != (Cn, T):
+        raise L.DasacError("view_consistency: tables of C={}, T={} for a tensor of C={}, T={}".format(tables.C, tables.T, Cn, T))
+    aligned = _c(aligned)
+    with PROFILE.span("view_consistency", 0.0, None, aligned.numel() * 4.0):
+        L.check(lib.dasac_view_consistency(aligned.data_ptr(), NT // T, T, Cn, H * W, float(cover), tables.agree.data_ptr(),
+                                           tables.flips.data_ptr(), tables.per_view.data_ptr(), L.stream_ptr()),
+                "dasac_view_consistency")
+    return tables
+
+
 VIS_IMAGE, VIS_LABELS, VIS_SCORES, VIS_CONF = 0, 1, 2, 3
 
 

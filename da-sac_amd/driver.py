@@ -62,7 +62,11 @@ def train_epoch(net, optim, loader_source, loader_target, cfg_model, group_size,
     baseline mode runs the source step and the no-grad target forward (AdaBN, :281-289); SAC mode refreshes the momentum
     teacher on every NET_MOMENTUM_ITER-th iteration of the epoch (`update_teacher = i % NET_MOMENTUM_ITER == 0`, :294), skips
     the source pass under TRAIN.TARGET_ONLY (:274-276).  Batches are what the reference's loaders yield, already on the device:
-    (image, masks_gt) and (frames1, frames_gt, frames2, affine, affine_inv).  Returns the number of iterations."""
+    (image, masks_gt) and (frames1, frames_gt, frames2, affine, affine_inv).  Returns the number of iterations.
+
+    To watch the teacher's view consistency over a run (no labels needed), call `core.collect_consistency(True)` once and read
+    `core.consistency_tables(reset=True)` at the logging interval from `on_iteration` (summarise_consistency, format_consistency):
+    one more launch per target step."""
     n = 0
     for i, (batch_source, batch_target) in enumerate(zip(loader_source, loader_target)):
         if cfg_model.BASELINE:
@@ -166,7 +170,10 @@ def sac_train_iteration(net, optim, src_batch, tgt_batch, group_size, update_tea
     student -- the same gradient sum, half the launches, one gradient all-reduce per iteration).  Needs the bare module or
     `dasac_hip.parallel.OverlappedDataParallel`; silently runs the two-pass order where it does not apply (target_only, stock
     DistributedDataParallel, batch-statistics BN, crops of different sizes, or a concatenated batch whose largest activation
-    would leave the kernels' 4 GiB addressing window (FCN-8s at 16 crops of 512x1024 peaks at exactly 2 GiB: fused since round 5)."""
+    would leave the kernels' 4 GiB addressing window (FCN-8s at 16 crops of 512x1024 peaks at exactly 2 GiB: fused since round 5).
+
+    View consistency: after `core.collect_consistency(True)` (once) every target step, fused or not, adds its groups to the
+    label-free agreement tables -- one more launch per target step; read `core.consistency_tables(reset=True)` when logging."""
     core = net.module if hasattr(net, "module") else net
     if fuse_passes and not target_only and hasattr(net, "forward_fused") and hasattr(core, "backbone") and core.backbone._bn_frozen() \
             and tuple(src_batch[0].shape[1:]) == tuple(tgt_batch[0].shape[1:]) \
@@ -594,6 +601,82 @@ def format_confusion(matrix, names):
     return "\n".join(lines)
 
 
+def summarise_consistency(tables, ignore_classes=(), top=10):
+    """Reading of the view-consistency tables (`validation(..., consistency=True).consistency`, or `SAC.consistency_tables()`: a
+    dict or anything with agree / flips / per_view, host or device; the result is plain host numbers).  Per pixel the kernel counted
+    k, the teacher views that cover it, the consensus class c* (arg-max of the summed views) and m, the covered views whose own
+    arg-max is c*: agree[c*][k][m], and agree[C][0][0] where no view reaches.  Every share below counts the pixels with k >= 2
+    only -- a pixel seen by one view cannot disagree.  Returns a dict:
+      classes               one dict per class c: pixels (k >= 2), agreement = sum m / sum k, unanimous = share with m == k, by_k =
+                            [T+1] shares of those pixels seen by exactly k views (entries 0 and 1 are 0); all 0 without such pixels;
+      agreement             sum_c pixels_c * agreement_c / sum_c pixels_c over the classes not in `ignore_classes`: pixel-weighted;
+      class_mean_agreement  the plain mean of agreement_c over the classes not ignored that have any k >= 2 pixel;
+      classes_present       how many those are;
+      uncovered_share       agree[C][0][0] over all pixels;
+      flips                 the `top` largest off-diagonal entries of flips + flips^T (a pair of covered views whose arg-maxes are a
+                            and b, in either order): dicts with a < b, pairs, share_a and share_b = pairs over all pairs that involve
+                            a (b), the agreeing ones on the diagonal included; largest first, ties by (a, b); ignored classes left out;
+      views                 one dict per view slot t: coverage = covered pixels / all pixels, agreement = covered pixels whose
+                            arg-max is c* / covered pixels.
+    `agreement` is a label-free score of a checkpoint, with one caveat that no table can remove: a COLLAPSED model that predicts one
+    class everywhere agrees with itself perfectly and scores 1.0.  `classes_present` stands next to the score for that reason --
+    read them together (and `flips`, which is empty in that case)."""
+    import numpy as np
+    get = (lambda k: tables[k]) if isinstance(tables, dict) else (lambda k: getattr(tables, k))
+    A, F, V = (get(k).detach().cpu().to(torch.int64).numpy() for k in ("agree", "flips", "per_view"))   # small host tables: numpy
+    C, T = A.shape[0] - 1, A.shape[1] - 1
+    ks = np.arange(T + 1, dtype=np.int64)
+    multi = A[:C, 2:]                                             # [C, T-1, T+1]: k >= 2
+    by_k_pixels = np.concatenate([np.zeros((C, min(2, T + 1)), np.int64), multi.sum(2)], 1)
+    pixels = multi.sum((1, 2))
+    sum_m, sum_k = (multi * ks[None, None, :]).sum((1, 2)), (multi.sum(2) * ks[None, 2:]).sum(1)
+    unanimous = sum((A[:C, k, k] for k in range(2, T + 1)), np.zeros(C, np.int64))
+
+    def share(num, den):
+        return np.where(den > 0, num / np.maximum(den, 1), 0.0)
+    agreement, una, by_k = share(sum_m, sum_k), share(unanimous, pixels), share(by_k_pixels, pixels[:, None])
+    classes = [dict(pixels=int(pixels[c]), agreement=float(agreement[c]), unanimous=float(una[c]), by_k=by_k[c].tolist())
+               for c in range(C)]
+    ignore = set(int(i) for i in ignore_classes)
+    kept = [c for c in range(C) if c not in ignore and int(pixels[c]) > 0]
+    kept_pixels = sum(int(pixels[c]) for c in kept)
+    total = int(A.sum())
+    S = F + F.T - np.diag(np.diagonal(F))
+    involved = S.sum(1)
+    entries = [(int(S[a, b]), a, b) for a in range(C) for b in range(a + 1, C)
+               if a not in ignore and b not in ignore and int(S[a, b]) > 0]
+    entries.sort(key=lambda t: (-t[0], t[1], t[2]))
+    flips = [dict(a=a, b=b, pairs=n, share_a=n / int(involved[a]), share_b=n / int(involved[b])) for n, a, b in entries[:top]]
+    views = [dict(coverage=int(V[t, 0]) / total if total else 0.0, agreement=int(V[t, 1]) / int(V[t, 0]) if int(V[t, 0]) else 0.0)
+             for t in range(T)]
+    return dict(classes=classes,
+                agreement=sum(int(pixels[c]) * float(agreement[c]) for c in kept) / kept_pixels if kept_pixels else 0.0,
+                class_mean_agreement=sum(float(agreement[c]) for c in kept) / len(kept) if kept else 0.0,
+                classes_present=len(kept), uncovered_share=int(A[C, 0, 0]) / total if total else 0.0, flips=flips, views=views)
+
+
+def format_consistency(summary, names):
+    """Fixed-width text table of a `summarise_consistency` result for the log: the scores, one row per class (`names`, C of them),
+    the most frequent flips and one row per view slot."""
+    names = [str(n) for n in names]
+    assert len(names) == len(summary["classes"]), (len(names), len(summary["classes"]))
+    head = max(len("class"), max(len(n) for n in names))
+    n_k = len(summary["classes"][0]["by_k"]) if names else 0
+    lines = ["view agreement {:.4f} (class mean {:.4f}, {} of {} classes present), uncovered {:.4f}".format(
+        summary["agreement"], summary["class_mean_agreement"], summary["classes_present"], len(names), summary["uncovered_share"])]
+    lines.append(" ".join(["class".ljust(head), "pixels".rjust(12), "agree".rjust(7), "unanim".rjust(7)] +
+                          ["k={}".format(k).rjust(6) for k in range(2, n_k)]))
+    for n, row in zip(names, summary["classes"]):
+        lines.append(" ".join([n.ljust(head), str(row["pixels"]).rjust(12), "{:.4f}".format(row["agreement"]).rjust(7),
+                               "{:.4f}".format(row["unanimous"]).rjust(7)] + ["{:.3f}".format(v).rjust(6) for v in row["by_k"][2:]]))
+    if summary["flips"]:
+        lines.append("flips: " + ", ".join("{} <-> {} {} ({:.3f} / {:.3f})".format(names[f["a"]], names[f["b"]], f["pairs"], f["share_a"],
+                                                                               f["share_b"]) for f in summary["flips"]))
+    lines.append("views: " + ", ".join("{}: covers {:.4f}, agrees {:.4f}".format(t, v["coverage"], v["agreement"])
+                                       for t, v in enumerate(summary["views"])))
+    return "\n".join(lines)
+
+
 def gradient_report(net, optim, table=None, top=10):
     """Reading of a gradient health table (`optim.tensor_stats` by default, or e.g. `optim.measure_tensor_stats()`; fp64
     [n_params, 8], dasac_hip.optim.TENSOR_STATS_COLUMNS, rows in the flattened `param_groups` order).  THE ONE PLACE that copies
@@ -763,7 +846,7 @@ def summarise_validation(counts, ignore_classes=()):
 
 
 def validation(net, loader, step="source", group_size=None, max_iter=None, ignore_classes=(), num_classes=19, num_groups=None,
-               confusion=False, reliability_bins=0):
+               confusion=False, reliability_bins=0, consistency=False, consistency_cover=0.5):
     """`Trainer.validation` (train.py:339-469) with its step function (`step` :119-155 or `_step_target` :211-250, train=False):
     eval mode under no_grad (the previous mode is restored), loss means, one (tp, fp, fn) table per mask layer, the per-class and
     class-subset summaries and the checkpoint score.  Neither the teacher nor the class prior is updated.
@@ -794,18 +877,33 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     (arg-max class, confidence bin, miss / hit: summarise_reliability; `logits_up` and `teacher_init` are binned by their soft-max
     maximum, `teacher_refined` by its winning probability) are filled; both are empty dicts otherwise.  `counts` then follows from
     the matrices (counts_from_confusion) and holds the same integers, so every other field is unchanged.  The tables share one
-    device buffer: they are summed over ranks and copied to the host as `table` is, once."""
+    device buffer: they are summed over ranks and copied to the host as `table` is, once.
+
+    Label-free, opt-in, step="target" only (ValueError otherwise): with `consistency` the pass switches the model's
+    view-consistency collection on (`SAC.collect_consistency`, coverage threshold `consistency_cover`) on a fresh accumulator --
+    one more launch per batch, ops.view_consistency on the T aligned teacher views -- and restores the model's previous switch
+    and accumulator afterwards.  The namespace's `consistency` is {"agree": int64 [C+1,T+1,T+1], "flips": [C,C], "per_view":
+    [T,2]} on the host, summed over ranks as `table` is (one buffer, one collective, one copy), and `consistency_summary` is
+    summarise_consistency of it (format_consistency renders it); {} and None when off.  Reported only: no other field, the
+    checkpoint score included, depends on it."""
     from types import SimpleNamespace
     import torch.distributed as dist
     from dasac_hip import ops
     assert step in ("source", "target"), step
+    if consistency and step != "target":
+        raise ValueError("validation: view consistency needs the teacher's aligned views, step='target' (got step={!r})".format(step))
     core = net.module if hasattr(net, "module") else net
+    if consistency and not hasattr(core, "swap_consistency"):
+        raise ValueError("validation: {} collects no view consistency".format(type(core).__name__))
     device = next(core.parameters()).device
     rank, world = _dist_state(None, None)
     was = core.training
     core.eval()
     joint, bins = bool(confusion) or int(reliability_bins) > 0, int(reliability_bins)
     layers, table, rows, keys, matrices, rel = None, None, [], None, None, None
+    cons, cons_was = None, None
+    if consistency:
+        cons_was = core.swap_consistency((True, consistency_cover, None))
     try:
         with torch.no_grad():
             for batch in validation_batches(loader, max_iter):
@@ -821,6 +919,10 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
                     layers = ([k for k in VALIDATION_SCORE_LAYERS if k in outs], [k for k in VALIDATION_LABEL_LAYERS if k in outs])
                     keys = sorted(losses)
                 scores, maps = [outs[k] for k in layers[0]], [outs[k] for k in layers[1]]
+                if consistency and scores[0].shape[1] != num_classes:
+                    # on EVERY rank, before any collective: a rank that owns no group sizes its zero tables from num_classes
+                    raise ValueError("validation: num_classes={} but the net has {} classes: the consistency tables of the ranks "
+                                     "would differ in size".format(num_classes, scores[0].shape[1]))
                 if joint:
                     if table is None:               # one buffer: [L][C+1][C+1] matrices, then [Ls][C][bins][2] reliability tables
                         n_mat, side = len(scores) + len(maps), num_classes + 1
@@ -834,8 +936,13 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
                 rows.append(torch.cat([losses[k].detach().mean().reshape(1) for k in keys]))
     finally:
         core.train(was)
+        if consistency:
+            cons = core.swap_consistency(cons_was)[2]
     if table is None:
-        return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0, confusion={}, reliability={})
+        return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0, confusion={}, reliability={},
+                               consistency={}, consistency_summary=None)
+    if consistency and cons is None:        # a rank that owns no group (views sharded over ranks) still takes part in the sum
+        cons = ops.consistency_tables(num_classes, group_size, device)
     names = layers[0] + layers[1]
     loss_rows = torch.stack(rows)
     multi = dist.is_available() and dist.is_initialized() and world > 1
@@ -848,7 +955,16 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
         if step == "target":
             dist.all_reduce(loss_rows)
             loss_rows = loss_rows / world
+        if consistency:
+            if dist.get_backend() == "gloo":
+                cons = cons.cpu()
+            dist.all_reduce(cons.buffer)
     table, loss_rows = table.cpu(), loss_rows.cpu().tolist()
+    cons_tables, cons_summary = {}, None
+    if consistency:
+        cons = cons.cpu()
+        cons_tables = {"agree": cons.agree, "flips": cons.flips, "per_view": cons.per_view}
+        cons_summary = summarise_consistency(cons_tables, ignore_classes)
     conf_tables, rel_tables = {}, {}
     if joint:
         side = num_classes + 1
@@ -862,7 +978,7 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     per_class, mean, score = summarise_validation(counts, ignore_classes)
     losses = {k: stat_mean([row[i] for row in loss_rows]) for i, k in enumerate(keys)}
     return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score,
-                           confusion=conf_tables, reliability=rel_tables)
+                           confusion=conf_tables, reliability=rel_tables, consistency=cons_tables, consistency_summary=cons_summary)
 
 
 # --------------------------------------------------------------------------------------------------

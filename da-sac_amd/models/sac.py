@@ -17,6 +17,13 @@ from .basenet import BaseNet
 _EMA_KEYS = ("weight", "bias", "running_mean", "running_var")
 
 
+def consistency_owner(rank, B, T):
+    """Whether `rank`, holding B views per step, adds its groups to the view-consistency tables.  With whole groups on a rank
+    (B >= T) every rank counts its own.  With a group's T views spread over T // B consecutive ranks, each of them holds the same
+    gathered tensor of all T views: the rank that holds the group's first view counts it, so every group is counted once."""
+    return B >= T or (rank * B) % T == 0
+
+
 class SAC_Baseline(BaseNet):
     """Source-only / AdaBN wrapper (sac.py:15-38)."""
 
@@ -56,6 +63,8 @@ class SAC(SAC_Baseline):
         # arithmetic, label maps bit-equal on equal probabilities, one 19-float round trip per target step.  True: on the device in
         # the class-prior kernel (within 1 ULP, no host synchronisation: see ops.DeviceClassVectors)
         self.device_thresholds = False
+        # view-consistency collection (collect_consistency): plain attributes, not buffers -- state_dict() does not see them
+        self._consistency_on, self._consistency_cover, self._consistency = False, 0.5, None
         self._exempt_frozen_bn_buffers_from_ddp_broadcast()
 
     def _exempt_frozen_bn_buffers_from_ddp_broadcast(self):
@@ -93,6 +102,30 @@ class SAC(SAC_Baseline):
             for b in bufs:
                 b.copy_(flat[o:o + b.numel()].view(b.shape))
                 o += b.numel()
+
+    # ------------------------------------------------------------------ view consistency (no counterpart in the reference)
+    def collect_consistency(self, on=True, cover=0.5):
+        """Switches the label-free view-consistency tables on or off.  While on, every pooled target pass (`forward` with
+        use_teacher, `forward_fused`) adds the agreement of its groups' T aligned teacher views to one device accumulator with
+        one more launch (ops.view_consistency: a view counts at a pixel where its coverage is >= `cover`); read it with
+        `consistency_tables`.  Off (the default) nothing is launched, allocated or computed.  Switching keeps the accumulator."""
+        self._consistency_on, self._consistency_cover = bool(on), float(cover)
+
+    def consistency_tables(self, reset=False):
+        """The accumulated ops.ConsistencyTables on the device (agree, flips, per_view: views of one int64 buffer), or None when
+        nothing has been collected.  `reset` hands the tables over and starts a fresh accumulator with the next target pass.  Under
+        data parallelism each rank holds the counts of the groups it owns (consistency_owner): sum the buffers over ranks."""
+        tables = self._consistency
+        if reset:
+            self._consistency = None
+        return tables
+
+    def swap_consistency(self, state):
+        """Installs `state` = (on, cover, tables or None) and returns the state it replaces, accumulator included: how a pass
+        that collects for itself (`driver.validation(consistency=True)`) borrows the switch and gives it back as it was."""
+        was = (self._consistency_on, self._consistency_cover, self._consistency)
+        self._consistency_on, self._consistency_cover, self._consistency = bool(state[0]), float(state[1]), state[2]
+        return was
 
     def _get_op(self, name):
         op_name = "_{}".format(name)
@@ -227,10 +260,14 @@ class SAC(SAC_Baseline):
                                    "(sac.py:222 fails in the reference)".format(self.cfg.CONF_POOL, T, B))
             probs_g, aff_g, inv_g = self._gather(probs, T), self._gather(affine, T), self._gather(affine_inv, T)
             pooled, mask, aligned_g = ops.warp_pool(probs_g, aff_g, inv_g, T, self.cfg.CONF_POOL, want_aligned=True)
+            if self._consistency_on and consistency_owner(self.rank, B, T):      # every rank of the group holds this tensor
+                self._consistency = ops.view_consistency(aligned_g, T, self._consistency, self._consistency_cover)
             lo = (self.rank * B) % T
             diags["teacher_aligned"] = aligned_g[lo:lo + B].contiguous()
         else:
             pooled, mask, aligned = ops.warp_pool(probs, affine, affine_inv, T, self.cfg.CONF_POOL, want_aligned=True)
+            if self._consistency_on:
+                self._consistency = ops.view_consistency(aligned, T, self._consistency, self._consistency_cover)
             diags["teacher_aligned"] = aligned
         if debug:
             diags["frames_aligned"] = ops.warp_affine(frames, affine)

@@ -591,6 +591,31 @@ int dasac_confusion_counts(const float* scores0, const float* scores1, const flo
                            int64_t HW, int ignore_index, int64_t* confusion, int64_t* reliability, int n_bins, int softmax_mask,
                            dasac_stream_t stream);
 
+/* Label-free view consistency: how far the T aligned teacher views of a target image agree -- the signal the method trains on,
+ * counted; a diagnostic the reference does not have.  aligned: fp32 [N*T][C][HW], view t of group n at index n*T + t: the tensor
+ * dasac_warp_pool writes (`aligned`), probabilities in the reference frame, zero where a view does not reach.  Per group n, pixel p
+ * and view t:
+ *   z_t      the fp32 sum of the view's C values at the pixel, added one class after another in ascending c: the view's bilinear
+ *            coverage there (1 inside, 0 outside, fractional on the rim and next to zeroed padding);
+ *   covered  z_t >= cover (0.5: more than half of the tap weight is real);
+ *   a_t      the arg-max over c of the view's values, first maximum wins (strict >);
+ *   k        the number of covered views;
+ *   c*       the consensus: the arg-max over c of sum_t aligned[n,t,c,p], an fp32 sum over ALL t in ascending order, first maximum
+ *            wins -- uncovered views add their zeros or rim weights exactly as they do in the pooled sum;
+ *   m        the number of covered views with a_t == c*.
+ * Three int64 tables, ACCUMULATED into (the caller zeroes them or keeps accumulating):
+ *   agree    [C+1][T+1][T+1]: every pixel adds 1 at [c*][k][m] when k >= 1 and at [C][0][0] when k == 0: one call adds N*HW in all;
+ *   flips    [C][C]: every pair t < u of views that are both covered adds 1 at [a_t][a_u]; the diagonal holds the agreeing pairs
+ *            (the host symmetrises the matrix);
+ *   per_view [T][2]: slot t counts the pixels where it is covered, and those where it is covered and a_t == c*.
+ * 1 <= T <= DASAC_CONSISTENCY_MAX_VIEWS, 1 <= C <= 32, N > 0, 0 < HW < 2^30 (dasac_warp_pool's own limit) and N*T < 2^31; offsets
+ * are 64-bit.  Pointers are non-NULL and aligned to their element size; anything else is DASAC_EINVAL before any launch.  Integer
+ * adds only: exact and bit-identical from run to run.  No load leaves its (n, t, c) plane (HW needs no alignment).  One launch on
+ * `stream`; no workspace, no allocation, no synchronisation. */
+#define DASAC_CONSISTENCY_MAX_VIEWS 8
+int dasac_view_consistency(const float* aligned, int N, int T, int C, int64_t HW, float cover, int64_t* agree, int64_t* flips,
+                           int64_t* per_view, dasac_stream_t stream);
+
 /* Per-image class statistics for importance-sampled target selection (tools/compute_IS_weights.py:58-83, on the device):
  * counts[b][v] += number of pixels of image b with value v, v in 0..255 (value 255 is counted too; callers drop it).
  * labels: [B][HW] uint8, any alignment (an unaligned head and a tail of any length per image are read byte by byte, the
