@@ -14,6 +14,9 @@ tape inside the backbone -- backward, calling only the C-ABI kernels of libdasac
 
 The whole plan is exposed to PyTorch as ONE autograd.Function (inputs: image + all parameters), so
 DistributedDataParallel sees ordinary parameter gradients.
+
+`Engine.probe` (None by default; `driver.activation_probe` attaches one) turns a forward into a probed one: every activation
+is kept until the end of the pass and one dasac_activation_stats call reduces them per channel and sample segment.
 """
 import torch
 
@@ -457,6 +460,7 @@ class Engine:
         self.last_use[plan.output] = len(plan.ops)
         self._tables, self._packs, self._folds = {}, {}, {}
         self._refresh, self._fold_bufs = {}, {}
+        self.probe, self._layouts = None, {}      # activation tables: off unless a probe is attached (Engine.forward)
         # A ReLU conv's pattern is recorded as bits when the backward pass will apply it in a stride-1 data-gradient epilogue:
         # the mask is applied by the consumer that finishes LAST in backward order = the slot's FIRST consumer in plan order.
         self._bits_wanted = [False] * plan.n_slots
@@ -628,18 +632,77 @@ class Engine:
 
     # ---------------------------------------------------------------- forward
     def forward(self, x, keep):
-        """Runs the plan.  keep=True retains what backward needs; returns (output, saved)."""
+        """Runs the plan.  keep=True retains what backward needs; returns (output, saved).
+
+        With a `probe` attached (None by default: nothing below happens) every activation of the pass stays alive until its
+        end -- on keep=False passes too, which then need the memory of a training pass instead of that of the two or three
+        live slots -- and ONE dasac_activation_stats call over slot 0 (the input) and every op's output, in plan order, follows
+        the last op on the launch stream.  `probe.append((table, layout, N, bounds))` receives the device table (fp64
+        [n_segments, R, 6], ops.ACTIVATION_STATS_COLUMNS), the layout (`activation_layout`), the batch size and the segment
+        bounds (`probe.bounds`: None, cut points, or a callable N -> bounds).  Nothing synchronises; `saved` is what it is
+        without a probe."""
         L.require_gpu(x)
         self.refresh(x.device, transposed=keep)
         acts = {0: x}
         saved = {"acts": acts, "aux": {}, "bits": {}}
+        probe = self.probe
+        held = None if probe is None else [x]
         for i, op in enumerate(self.plan.ops):
             acts[op.dst] = op.forward(self, i, saved, keep)
+            if held is not None:
+                held.append(acts[op.dst])
             if not keep:
                 for s in op.inputs():
                     if self.last_use[s] == i and s != 0:
                         del acts[s]
+        if held is not None:
+            self._probe_pass(probe, held)
         return acts[self.plan.output], saved
+
+    # ---------------------------------------------------------------- activation tables
+    def activation_layout(self, shapes, names=None):
+        """One entry per tensor of a probed pass -- slot 0, then every op's output in plan order -- for tensors of `shapes`
+        ((C, H, W) each): dict(op (index, -1 for the input), slot, name, kind, C, H, W, relu (a ReLU closes it), row0 (its first
+        table row)).  names: {conv module: name}, e.g. inverted `named_modules()`; a conv op is called by its module (the common
+        dotted prefix of the branches for a multi-branch op), the other ops "pool@<slot>" / "up2add@<slot>" / "dropout@<slot>", the
+        input "input".  A name that is missing or taken gets "@<slot>" appended: names are unique."""
+        names = names or {}
+        entries, row0, taken = [], 0, set()
+        for j, (c, h, w) in enumerate(shapes):
+            op = None if j == 0 else self.plan.ops[j - 1]
+            slot = 0 if op is None else op.dst
+            if op is None:
+                name, kind = "input", "input"
+            elif isinstance(op, ConvOp):
+                parts = [names[m].split(".") for m in op.convs if m in names]
+                common = []
+                if len(parts) == len(op.convs):
+                    for level in zip(*parts):
+                        if any(p != level[0] for p in level):
+                            break
+                        common.append(level[0])
+                name, kind = ".".join(common) or "conv@{}".format(slot), op.kind
+            else:
+                name, kind = "{}@{}".format("dropout" if op.kind == "drop" else op.kind, slot), op.kind
+            if name in taken:
+                name = "{}@{}".format(name, slot)
+            taken.add(name)
+            entries.append(dict(op=j - 1, slot=slot, name=name, kind=kind, C=int(c), H=int(h), W=int(w),
+                                relu=bool(op is not None and op.relu), row0=row0))
+            row0 += int(c)
+        return entries
+
+    def _probe_pass(self, probe, held):
+        N = held[0].shape[0]
+        bounds = probe.bounds(N) if callable(probe.bounds) else probe.bounds
+        shapes = tuple(tuple(t.shape[1:]) for t in held)
+        plan = ops.activation_stats_plan(shapes, N, bounds)
+        names = getattr(probe, "names", None)
+        key = (shapes, id(names))
+        ent = self._layouts.get(key)
+        if ent is None:
+            ent = self._layouts[key] = (names, self.activation_layout(shapes, names))      # (names held: its id stays its own)
+        probe.append((plan.run(held), ent[1], N, plan.bounds))
 
     # ---------------------------------------------------------------- backward
     def backward(self, saved, grad_out, need, trace=None, sink=None):

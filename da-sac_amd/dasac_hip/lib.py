@@ -65,6 +65,8 @@ PROTOTYPES = {
     "dasac_adam_step_ctl": (_i, [_p, _i, _p, _i, _p, _i, C.c_double, C.c_double, C.c_double, _p, _i, _i, _p]),
     "dasac_tensor_stats_workspace": (_sz, [_i]),
     "dasac_tensor_stats": (_i, [_p, _i, _i, _p, _i, _p, _i, _p, _sz, _p, _p, _p, _p, _p, _p]),
+    "dasac_activation_stats_workspace": (_sz, [_l]),
+    "dasac_activation_stats": (_i, [_p, _i, _i, _i, _p, _i, _p, _sz, _p, _p]),
     "dasac_scale_planes": (_i, [_p, _p, _l, _l, _p, _p]),
     "dasac_add": (_i, [_p, _p, _p, _l, _p]),
     "dasac_relu_mask": (_i, [_p, _p, _p, _l, _p]),

@@ -1388,6 +1388,102 @@ def view_consistency(aligned, T, tables=None, cover=0.5):
     return tables
 
 
+# ----------------------------------------------------------------------------------------------
+# per-layer activation tables (include/dasac_hip.h: dasac_activation_stats)
+# ----------------------------------------------------------------------------------------------
+# columns of an activation table row; per (segment, channel)
+ACTIVATION_STATS_COLUMNS = ("sum", "sumsq", "maxabs", "nonfinite", "first_nonfinite", "zeros")
+ACTIVATION_STATS_MAX_SEGMENTS, ACTIVATION_STATS_MAX_PLANE = 8, 1 << 30
+
+
+def segment_bounds(bounds, N):
+    """The sample segments of an activation table as the full tuple (0, ..., N).  `bounds`: None (one segment), the full tuple, or
+    the interior cut points alone ((n_src,) for a [source; target] batch).  Refuses what the kernel could not check itself (the
+    table lives in device memory): not strictly ascending, not ending at N, more than ACTIVATION_STATS_MAX_SEGMENTS segments."""
+    N = int(N)
+    b = () if bounds is None else tuple(int(v) for v in bounds)
+    if not b or b[0] != 0:
+        b = (0,) + b + (N,)
+    if N < 1 or b[-1] != N or any(hi <= lo for lo, hi in zip(b, b[1:])) or len(b) - 1 > ACTIVATION_STATS_MAX_SEGMENTS:
+        raise L.DasacError("activation_stats: segment bounds must ascend strictly from 0 to N={} in at most {} segments (got {})".format(
+            N, ACTIVATION_STATS_MAX_SEGMENTS, bounds))
+    return b
+
+
+class ActivationStatsPlan:
+    """Descriptor layout of one dasac_activation_stats call: built on the host once per (shapes, N, bounds) -- `activation_stats_plan`
+    caches it -- the segment bounds uploaded once per device, the tensors' pointers patched into a copy of the rows per call.
+    shapes: (C, H, W) or (C, HW) per tensor, each a contiguous fp32 [N, C, H, W]; bounds: see `segment_bounds`.
+    rows (numpy, the 32-byte records of the header), row0 / plane0 (prefix sums of C / N*C), R, n_planes and bytes_read are plain host
+    data: building a plan needs no device."""
+
+    def __init__(self, shapes, N, bounds=None):
+        import numpy as np
+        self.N, self.bounds = int(N), segment_bounds(bounds, N)
+        self.shapes = tuple((int(s[0]), int(np.prod(s[1:], dtype=np.int64))) for s in shapes)
+        if not self.shapes or any(c < 1 or not 1 <= hw <= ACTIVATION_STATS_MAX_PLANE for c, hw in self.shapes):
+            raise L.DasacError("activation_stats: at least one tensor, C >= 1 and 1 <= H*W <= 2^30 (got {})".format(list(shapes)))
+        self.rows = np.zeros(len(self.shapes), dtype=np.dtype([("x", "<u8"), ("HW", "<i8"), ("C", "<i4"), ("row0", "<i4"), ("plane0", "<i8")]))
+        assert self.rows.dtype.itemsize == 32
+        cs = np.asarray([c for c, _ in self.shapes], dtype=np.int64)
+        self.rows["HW"], self.rows["C"] = [hw for _, hw in self.shapes], cs
+        self.rows["row0"], self.rows["plane0"] = np.cumsum(cs) - cs, (np.cumsum(cs) - cs) * self.N
+        self.row0, self.plane0 = [int(v) for v in self.rows["row0"]], [int(v) for v in self.rows["plane0"]]
+        self.R = int(cs.sum())
+        self.n_planes = self.N * self.R
+        if self.n_planes >= 1 << 31:
+            raise L.DasacError("activation_stats: {} planes exceed one launch".format(self.n_planes))
+        self.bytes_read = 4.0 * self.N * sum(c * hw for c, hw in self.shapes)
+        self._bounds_dev = {}
+
+    def run(self, tensors):
+        """The table of `tensors` (fp32 cuda [N, C, ...] in the plan's order), a new fp64 [n_segments, R, 6] device tensor; two launches
+        on the current stream, no synchronisation."""
+        import numpy as np
+        lib = L.load()
+        L.require_gpu(*tensors)
+        if len(tensors) != len(self.shapes):
+            raise L.DasacError("activation_stats: the plan has {} tensors (got {})".format(len(self.shapes), len(tensors)))
+        held = []
+        for t, (c, hw) in zip(tensors, self.shapes):
+            if t.dtype != torch.float32 or t.dim() < 2 or tuple(t.shape[:2]) != (self.N, c) or t.numel() != self.N * c * hw:
+                raise L.DasacError("activation_stats: expected float32 [{}, {}, {}] (got {} {})".format(self.N, c, hw, t.dtype, tuple(t.shape)))
+            held.append(_c(t))
+        dev = held[0].device
+        seg = self._bounds_dev.get(dev.index)
+        if seg is None:
+            seg = self._bounds_dev[dev.index] = torch.tensor(self.bounds, dtype=torch.int32).to(dev)
+        rows = self.rows.copy()
+        rows["x"] = [t.data_ptr() for t in held]
+        # fresh activations every pass, so the pointers are new every call: through pinned memory, without blocking (optim._table)
+        table_rows = torch.from_numpy(rows.view(np.int64)).pin_memory().to(dev, non_blocking=True)
+        S = len(self.bounds) - 1
+        table = torch.empty((S, self.R, len(ACTIVATION_STATS_COLUMNS)), dtype=torch.float64, device=dev)
+        ws = L.workspace(lib.dasac_activation_stats_workspace(self.n_planes), dev)
+        with PROFILE.span("activation_stats", 0.0, None, self.bytes_read):
+            L.check(lib.dasac_activation_stats(table_rows.data_ptr(), len(held), self.N, self.R, seg.data_ptr(), S, ws.data_ptr(),
+                                               ws.numel(), table.data_ptr(), L.stream_ptr()), "dasac_activation_stats")
+        return table
+
+
+_activation_plans = {}
+
+
+def activation_stats_plan(shapes, N, bounds=None):
+    """The cached ActivationStatsPlan of (shapes, N, bounds)."""
+    key = (tuple(tuple(int(v) for v in s) for s in shapes), int(N), segment_bounds(bounds, N))
+    plan = _activation_plans.get(key)
+    if plan is None:
+        plan = _activation_plans[key] = ActivationStatsPlan(key[0], key[1], key[2])
+    return plan
+
+
+def activation_stats(tensors, bounds=None):
+    """dasac_activation_stats over a list of fp32 [N, C, ...] tensors: (table fp64 [n_segments, sum C, 6], plan)."""
+    plan = activation_stats_plan([tuple(t.shape[1:]) for t in tensors], tensors[0].shape[0], bounds)
+    return plan.run(tensors), plan
+
+
 VIS_IMAGE, VIS_LABELS, VIS_SCORES, VIS_CONF = 0, 1, 2, 3
 
 

@@ -761,6 +761,219 @@ def format_gradient_report(report, top=10):
     return "\n".join(lines)
 
 
+# --------------------------------------------------------------------------------------------------
+# activation tables: per-layer activation health and the source / target domain gap (no counterpart in the reference)
+# --------------------------------------------------------------------------------------------------
+class ActivationRecord:
+    """One probed engine forward: net ("backbone" / "slow_net"), N (batch size), bounds (the full segment tuple (0, ..., N)),
+    table (device fp64 [n_segments, R, 6], dasac_hip.ops.ACTIVATION_STATS_COLUMNS) and layout (`Engine.activation_layout`)."""
+
+    def __init__(self, net, N, bounds, table, layout):
+        self.net, self.N, self.bounds, self.table, self.layout = net, int(N), tuple(bounds), table, layout
+
+    def __repr__(self):
+        return "ActivationRecord(net={!r}, N={}, bounds={}, layers={})".format(self.net, self.N, self.bounds, len(self.layout))
+
+
+class ActivationProbe:
+    """What `activation_probe` yields: `passes` lists one ActivationRecord per engine forward inside the block, in call order."""
+
+    def __init__(self, bounds=None):
+        self.bounds, self.passes = bounds, []
+
+
+class _ProbeTap:
+    """The probe as one engine sees it (Engine.forward): the shared bounds, this net's module names, records tagged with its net."""
+
+    def __init__(self, probe, net, names):
+        self.probe, self.net, self.names = probe, net, names
+
+    @property
+    def bounds(self):
+        return self.probe.bounds
+
+    def append(self, item):
+        table, layout, N, bounds = item
+        self.probe.passes.append(ActivationRecord(self.net, N, bounds, table, layout))
+
+
+def _probed_nets(net):
+    core = net.module if hasattr(net, "module") else net
+    nets = [("backbone", core.backbone if hasattr(core, "backbone") else core)]
+    if hasattr(core, "slow_net"):
+        nets.append(("slow_net", core.slow_net))
+    return nets
+
+
+class activation_probe:
+    """Context manager: per-layer activation tables of every backbone forward inside the block.
+
+        with driver.activation_probe(net, bounds=(n_src,)) as probe:
+            driver.sac_train_iteration(net, optim, src, tgt, T, update, lr_target, fuse_passes=True)
+        report = driver.domain_gap_report(probe.passes[-1])           # the student over [source; target]
+
+    Attaches one probe to the engines of `backbone` and, for SAC, `slow_net` (through `.module` of a DistributedDataParallel /
+    OverlappedDataParallel wrapper) and detaches it on exit.  While attached, every engine forward keeps all its activations
+    until its end (a no-grad pass then needs the memory of a training pass) and adds one dasac_activation_stats call: two launches,
+    no synchronisation, no ATen arithmetic; losses, logits and gradients are bit for bit what they are without it.  `probe.passes`:
+    one ActivationRecord per forward, in call order (a two-pass SAC iteration: student source, student target, teacher; with
+    fuse_passes: teacher, student over the concatenated batch).
+    bounds: None (one segment), the interior cut points of the batch ((n_src,)), or a callable N -> bounds for passes of different
+    sizes.  Replacing a module's Parameter objects inside the block (which re-captures the engine) drops the probe.
+    Tables are PER RANK: columns sum, sumsq, nonfinite and zeros add across ranks, maxabs takes the maximum, and first_nonfinite
+    is an index into the rank's own batch -- reduce them yourself where a global view is wanted."""
+
+    def __init__(self, net, bounds=None):
+        self.net, self.probe, self._engines = net, ActivationProbe(bounds), []
+
+    def __enter__(self):
+        from dasac_hip import engine as E
+        for tag, sub in _probed_nets(self.net):
+            if sub._engine is None or sub._engine.stale():
+                sub._engine = E.Engine(sub._plan())
+            if sub._engine.probe is not None:
+                self.__exit__()
+                raise RuntimeError("activation_probe: {} already has a probe attached".format(tag))
+            sub._engine.probe = _ProbeTap(self.probe, tag, {m: name for name, m in sub.named_modules()})
+            self._engines.append(sub._engine)
+        return self.probe
+
+    def __exit__(self, *exc):
+        for eng in self._engines:
+            eng.probe = None
+        self._engines = []
+        return False
+
+
+def activation_stats(net, images, bounds=None, teacher=False):
+    """The stand-alone form: one no-grad forward of the student backbone (teacher=True: the momentum teacher) over `images`
+    [N,3,H,W] with a probe attached; returns its ActivationRecord.  bounds as in `activation_probe`."""
+    nets = dict(_probed_nets(net))
+    with torch.no_grad(), activation_probe(net, bounds) as probe:
+        nets["slow_net" if teacher else "backbone"](images)
+    assert len(probe.passes) == 1
+    return probe.passes[0]
+
+
+def _host_table(record):
+    import numpy as np
+    T = record.table
+    T = T.detach().cpu().to(torch.float64).numpy() if isinstance(T, torch.Tensor) else np.asarray(T, dtype=np.float64)
+    R = sum(e["C"] for e in record.layout)
+    assert T.ndim == 3 and T.shape == (len(record.bounds) - 1, R, 6), (T.shape, len(record.bounds) - 1, R)
+    return T
+
+
+def activation_report(record, segment=0, top=10):
+    """Reading of one segment of an activation table.  THE ONE PLACE that copies it to the host -- a synchronisation: call it when
+    logging.  Returns a plain dict:
+      layers   one dict per tensor in plan order: name, kind, shape (n, C, H, W with n the segment's samples), mean and std over
+               the finite entries of all channels, maxabs, zero_share (zeros / elements), dead_channels (channels whose every
+               entry is 0: a dead ReLU unit), nonfinite (count) and first_nonfinite ((n, c, y, x) in the tensor, or None);
+      first_nonfinite_layer   the name of the first layer in plan order with non-finite entries, or None: where a fault began;
+      top      the names of the `top` layers by maxabs, largest first (ties in plan order);
+      net, segment, samples (first, one past the last)."""
+    import math
+    import numpy as np
+    T = _host_table(record)[segment]
+    lo, hi = record.bounds[segment], record.bounds[segment + 1]
+    layers = []
+    for e in record.layout:
+        rows = T[e["row0"]:e["row0"] + e["C"]]
+        per_channel = (hi - lo) * e["H"] * e["W"]
+        total, finite = per_channel * e["C"], per_channel * e["C"] - float(rows[:, 3].sum())
+        mean = float(rows[:, 0].sum()) / finite if finite > 0 else 0.0
+        var = max(float(rows[:, 1].sum()) / finite - mean * mean, 0.0) if finite > 0 else 0.0
+        firsts = rows[:, 4][rows[:, 4] > 0]
+        first = tuple(int(v) for v in np.unravel_index(int(firsts.min()) - 1, (record.N, e["C"], e["H"], e["W"]))) if len(firsts) else None
+        layers.append(dict(name=e["name"], kind=e["kind"], shape=(hi - lo, e["C"], e["H"], e["W"]), mean=mean, std=math.sqrt(var),
+                           maxabs=float(rows[:, 2].max()), zero_share=float(rows[:, 5].sum()) / total,
+                           dead_channels=int((rows[:, 5] == per_channel).sum()), nonfinite=int(rows[:, 3].sum()), first_nonfinite=first))
+    bad = [l["name"] for l in layers if l["nonfinite"]]
+    order = sorted(range(len(layers)), key=lambda i: (-layers[i]["maxabs"], i))
+    return dict(layers=layers, first_nonfinite_layer=bad[0] if bad else None, top=[layers[i]["name"] for i in order[:top]],
+                net=record.net, segment=segment, samples=(lo, hi))
+
+
+def domain_gap_report(a, b=None, top=10):
+    """Per-layer covariate shift between two domains under the same weights: two records of the same net (segment 0 of each), or
+    ONE record with two segments (segments 0 and 1: `forward_fused`'s [source; target] batch).  Copies the tables to the host.
+    Per channel, with n elements per domain: mu = sum / n, var = max(sumsq / n - mu^2, 0), sigma = sqrt(var),
+      num = (mu_a - mu_b)^2 + (sigma_a - sigma_b)^2,  den = (var_a + var_b) / 2,  gap_c = 0 if num == 0 else num / max(den, 1e-30).
+    Returns a plain dict:
+      layers   one dict per tensor in plan order: name, kind, gap (mean of gap_c over the channels that are not dead -- all
+               zero -- in BOTH domains; 0 if none), gap_max and gap_max_channel, mean_shift (RMS over channels of mu_a - mu_b),
+               dead_only_a, dead_only_b, dead_both (channel counts);
+      top      the names of the `top` layers by gap, largest first (ties in plan order).
+    Refuses records whose layouts differ."""
+    import numpy as np
+    if b is None:
+        if len(a.bounds) < 3:
+            raise ValueError("domain_gap_report: one record needs two segments (got bounds {})".format(a.bounds))
+        b, sa, sb = a, 0, 1
+    else:
+        sa = sb = 0
+    same = lambda e: (e["name"], e["kind"], e["C"], e["H"], e["W"], e["row0"])
+    if [same(e) for e in a.layout] != [same(e) for e in b.layout]:
+        raise ValueError("domain_gap_report: the two records have different layouts")
+    Ta, Tb = _host_table(a)[sa], _host_table(b)[sb]
+    layers = []
+    for e in a.layout:
+        rows = slice(e["row0"], e["row0"] + e["C"])
+        na = float((a.bounds[sa + 1] - a.bounds[sa]) * e["H"] * e["W"])
+        nb = float((b.bounds[sb + 1] - b.bounds[sb]) * e["H"] * e["W"])
+        mu_a, mu_b = Ta[rows, 0] / na, Tb[rows, 0] / nb
+        var_a, var_b = np.maximum(Ta[rows, 1] / na - mu_a ** 2, 0.0), np.maximum(Tb[rows, 1] / nb - mu_b ** 2, 0.0)
+        num = (mu_a - mu_b) ** 2 + (np.sqrt(var_a) - np.sqrt(var_b)) ** 2
+        gap_c = np.where(num == 0, 0.0, num / np.maximum(0.5 * (var_a + var_b), 1e-30))
+        dead_a, dead_b = Ta[rows, 5] == na, Tb[rows, 5] == nb
+        alive = ~(dead_a & dead_b)
+        worst = int(np.argmax(gap_c))
+        layers.append(dict(name=e["name"], kind=e["kind"], gap=float(gap_c[alive].mean()) if alive.any() else 0.0,
+                           gap_max=float(gap_c[worst]), gap_max_channel=worst, mean_shift=float(np.sqrt(np.mean((mu_a - mu_b) ** 2))),
+                           dead_only_a=int((dead_a & ~dead_b).sum()), dead_only_b=int((dead_b & ~dead_a).sum()),
+                           dead_both=int((dead_a & dead_b).sum())))
+    order = sorted(range(len(layers)), key=lambda i: (-layers[i]["gap"], i))
+    return dict(layers=layers, top=[layers[i]["name"] for i in order[:top]], net=a.net)
+
+
+def _fixed_width(head, cols, width, names, cells):
+    lines = [" ".join(["layer".ljust(head)] + [c.rjust(w) for c, w in zip(cols, width)])]
+    for name, row in zip(names, cells):
+        lines.append(" ".join([name.ljust(head)] + [c.rjust(w) for c, w in zip(row, width)]))
+    return lines
+
+
+def format_activation_report(report, top=10):
+    """Fixed-width text table of an `activation_report` for the log: the `top` layers by maxabs, then every layer with non-finite
+    entries that is not among them (plan order), then one summary line."""
+    L_ = report["layers"]
+    by_max = sorted(range(len(L_)), key=lambda i: (-L_[i]["maxabs"], i))[:top]
+    rows = [L_[i] for i in by_max + [i for i, l in enumerate(L_) if l["nonfinite"] and i not in by_max]]
+    head = max([len("layer")] + [len(l["name"]) for l in rows])
+    cols, width = ["kind", "shape", "mean", "std", "max|x|", "zeros", "dead", "nonfinite", "first"], [6, 18, 11, 10, 10, 7, 5, 9, 5]
+    cells = [[l["kind"], "x".join(str(v) for v in l["shape"]), "{:.3e}".format(l["mean"]), "{:.3e}".format(l["std"]),
+              "{:.3e}".format(l["maxabs"]), "{:.4f}".format(l["zero_share"]), str(l["dead_channels"]), str(l["nonfinite"]),
+              "-" if l["first_nonfinite"] is None else str(l["first_nonfinite"])] for l in rows]
+    lines = _fixed_width(head, cols, width, [l["name"] for l in rows], cells)
+    lines.append("{} segment {} (samples {}..{}): {} layers; first layer with non-finite entries: {}".format(
+        report["net"], report["segment"], report["samples"][0], report["samples"][1] - 1, len(L_), report["first_nonfinite_layer"] or "none"))
+    return "\n".join(lines)
+
+
+def format_domain_gap_report(report, top=10):
+    """Fixed-width text table of a `domain_gap_report`: the `top` layers by gap, largest first, then one summary line."""
+    L_ = report["layers"]
+    rows = [L_[i] for i in sorted(range(len(L_)), key=lambda i: (-L_[i]["gap"], i))[:top]]
+    head = max([len("layer")] + [len(l["name"]) for l in rows])
+    cols, width = ["kind", "gap", "gap_max", "channel", "mean_shift", "dead_a", "dead_b", "dead_ab"], [6, 10, 10, 7, 10, 6, 6, 7]
+    cells = [[l["kind"], "{:.3e}".format(l["gap"]), "{:.3e}".format(l["gap_max"]), str(l["gap_max_channel"]), "{:.3e}".format(l["mean_shift"]),
+              str(l["dead_only_a"]), str(l["dead_only_b"]), str(l["dead_both"])] for l in rows]
+    lines = _fixed_width(head, cols, width, [l["name"] for l in rows], cells)
+    lines.append("{}: {} layers; largest gap: {}".format(report["net"], len(L_), rows[0]["name"] if rows else "none"))
+    return "\n".join(lines)
+
+
 def compute_sample_weights(net, batches, num_images, lut=None, teacher=False, scales=None, flip=False):
     """Stage 2 of the reference's schedule (tools/compute_IS_weights.py on the masks infer_val.py wrote) without leaving the
     device: per-image class pixel counts of the network's label maps, int64 [num_images,256] on the host -- the input of

@@ -461,6 +461,28 @@ int dasac_tensor_stats(const void* tensors, int row_bytes, int n_tensors, const 
                        const int32_t* row_of, int n_rows, void* workspace, size_t workspace_bytes, double* table,
                        const void* ctl, double* captured, int64_t* captured_at, const int64_t* skipped,
                        dasac_stream_t stream);
+/* Per-layer activation health / domain-gap table: one streaming pass over fp32 activations [N, C, H*W] that a forward pass
+ * already holds, reduced per channel and per sample segment.  `tensors`: a device array of n_tensors 32-byte rows
+ *   { const float* x; int64_t HW; int32_t C; int32_t row0; int64_t plane0; }
+ * each one contiguous tensor [N, C, HW], 1 <= HW <= 2^30 (a row outside that gives zeros); row0 / plane0 are the prefix sums of C / N*C over the earlier rows (row 0 has 0, 0), all
+ * tensors of a call share N, R = sum C is the number of channel rows and N*R the number of planes.  The rows live in device
+ * memory, so R is passed beside them: it sizes both grids and the workspace check.  `seg_bounds`: a device array of
+ * n_segments + 1 sample indices, strictly ascending from 0 to N, 1 <= n_segments <= 8; segment s covers samples
+ * seg_bounds[s] .. seg_bounds[s+1]-1 (device memory: the caller vouches for it; the kernel clamps what it reads to 0..N).
+ * table: [n_segments][R][6] doubles; for segment s and channel c of tensor t (row row0_t + c), over that segment's samples:
+ *   0 sum     sum x over finite x, each widened to double    3 nonfinite        number of Inf / NaN entries
+ *   1 sumsq   sum x^2 over finite x, squared in double       4 first_nonfinite  1 + flat NCHW index IN ITS TENSOR of the first
+ *   2 maxabs  max |x| over finite x, 0 if none                                  non-finite entry of the segment, 0 if none
+ *                                                            5 zeros            number of x == 0 (either sign)
+ * One 256-thread block per (tensor, sample, channel) plane writes one partial row to `workspace`
+ * (dasac_activation_stats_workspace(N*R) bytes); one wave per (segment, row) adds the segment's samples in ascending order.  No
+ * atomics, every combination in a fixed order, and an element's owner thread and a thread's summation order depend on the
+ * element's index inside its plane, never on its address: the same values give the same bits wherever each tensor lies (planes
+ * of 97 x 97 or 769 x 769 floats start on every 4-byte phase).  Bad arguments (null pointers; n_tensors, N, R or n_segments out
+ * of range; workspace too small) return DASAC_EINVAL before any launch and leave `table` untouched. */
+size_t dasac_activation_stats_workspace(int64_t n_planes);
+int dasac_activation_stats(const void* tensors, int n_tensors, int N, int R, const int32_t* seg_bounds, int n_segments,
+                           void* workspace, size_t workspace_bytes, double* table, dasac_stream_t stream);
 int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks,
                      float momentum, int update, double* sq, float* out, dasac_stream_t stream);
 int dasac_scale_planes(const float* x, const float* plane_scale, int64_t planes, int64_t HW,
