@@ -1323,6 +1323,58 @@ def confusion_counts(scores, label_maps, gt, confusion=None, reliability=None, b
     return confusion, reliability
 
 
+BOUNDARY_MAX_RADIUS = 16                                    # DASAC_BOUNDARY_MAX_RADIUS
+BOUNDARY_ROWS = ("tp", "fp", "fn", "pred", "both")          # dimension 2 of a boundary table
+
+
+def boundary_counts(scores, label_maps, gt, table=None, radius=8, ignore_index=255, num_classes=None):
+    """`mask_counts`' counts split by the distance to the nearest class contour (include/dasac_hip.h: dasac_boundary_counts).
+    scores: up to 4 fp32 [B,C,H,W] tensors (arg-max, first maximum wins); label_maps: up to 2 [B,H,W] maps, int64 or uint8 each (255 =
+    no label; a uint8 map is read as it is); gt int64 [B,H,W].  Accumulates into `table` (int64 [L,radius+1,5,C], scores first, then
+    label maps; allocated zeroed when None; a given table tells the radius) and returns it: slot s < radius holds the pixels at
+    Chebyshev distance s + 1 from a contour, slot `radius` everything further; rows BOUNDARY_ROWS -- tp, fp, fn by the pixel's slot
+    in the ground truth, pred by its slot in the predicted map, both (prediction == ground truth) by the larger of the two.  With
+    label maps only, C comes from `table` or `num_classes`.  driver.summarise_boundary reads the tables."""
+    lib = L.load()
+    scores, label_maps = list(scores or ()), list(label_maps or ())
+    L.require_gpu(gt, table, *scores, *label_maps)
+    n_layers = len(scores) + len(label_maps)
+    if n_layers == 0 or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
+        raise L.DasacError("boundary_counts takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
+            MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
+    if gt.dtype != torch.int64 or gt.dim() != 3:
+        raise L.DasacError("boundary_counts: gt must be int64 [B,H,W] (got {} {})".format(gt.dtype, tuple(gt.shape)))
+    B, H, W = gt.shape
+    if table is not None and (table.dtype != torch.int64 or table.dim() != 4):
+        raise L.DasacError("boundary_counts accumulates into an int64 [L,radius+1,5,C] tensor (got {} {})".format(table.dtype, tuple(table.shape)))
+    Cn = scores[0].shape[1] if scores else (table.shape[3] if table is not None else num_classes)
+    if Cn is None:
+        raise L.DasacError("boundary_counts: label maps alone do not tell the class count; pass table or num_classes")
+    radius = int(table.shape[1]) - 1 if table is not None else int(radius)
+    if not 1 <= radius <= BOUNDARY_MAX_RADIUS:
+        raise L.DasacError("boundary_counts: the radius must be in 1..{} (got {})".format(BOUNDARY_MAX_RADIUS, radius))
+    for s in scores:
+        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
+            raise L.DasacError("boundary_counts: a score tensor must be float32 {} (got {} {})".format((B, Cn, H, W), s.dtype, tuple(s.shape)))
+    for m in label_maps:
+        if m.dtype not in (torch.int64, torch.uint8) or tuple(m.shape) != (B, H, W):
+            raise L.DasacError("boundary_counts: a label map must be int64 or uint8 {} (got {} {})".format((B, H, W), m.dtype, tuple(m.shape)))
+    shape = (n_layers, radius + 1, len(BOUNDARY_ROWS), Cn)
+    if table is None:
+        table = torch.zeros(shape, dtype=torch.int64, device=gt.device)
+    elif tuple(table.shape) != shape or not table.is_contiguous():
+        raise L.DasacError("boundary_counts accumulates into a contiguous int64 {} tensor (got {} {})".format(shape, table.dtype, tuple(table.shape)))
+    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
+    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
+    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
+    u8_mask = sum(1 << i for i, m in enumerate(label_maps) if m.dtype == torch.uint8)
+    need = lib.dasac_boundary_counts_workspace(n_layers, B, H, W)
+    ws = L.workspace(need, gt.device)
+    L.check(lib.dasac_boundary_counts(*sp, *mp, u8_mask, gt.data_ptr(), B, Cn, H, W, radius, int(ignore_index), table.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), L.stream_ptr()), "dasac_boundary_counts")
+    return table
+
+
 CONSISTENCY_MAX_VIEWS, CONSISTENCY_MAX_CLASSES = 8, 32      # DASAC_CONSISTENCY_MAX_VIEWS; the kernel's class limit
 
 

@@ -456,7 +456,7 @@ def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="me
         return ops.infer_fuse(sources, flips, (H, W), mode, lut, want_conf, want_probs)
 
 
-def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confusion=False):
+def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confusion=False, boundary_radius=0):
     """mIoU over (image, label) batches: argmax + per-class tp/fp/fn in one kernel pass per batch
     (train.py:339-469, utils/metrics.py:9-53); counts are all-reduced when a process group exists.
     With `scales` (or `flip`) the prediction is infer_label_maps_ms's label map (scales defaults to (1.0,) when only `flip` is
@@ -464,13 +464,16 @@ def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confus
     map is widened to the int64 that counter reads, the one torch operation of that path.
     With `confusion` the pass is ops.confusion_counts instead -- it reads the uint8 map as it is -- the counts follow from the
     matrix (counts_from_confusion: the same integers) and the return value is (mIoU, iou, matrix int64 [C+1,C+1] on the host: row =
-    ground truth, column = prediction, index C = no class; see summarise_confusion)."""
+    ground truth, column = prediction, index C = no class; see summarise_confusion).
+    With `boundary_radius` R > 0 one ops.boundary_counts per batch runs beside that pass on the same prediction, and the return value
+    gains a last element: the boundary table int64 [R+1,5,C] on the host, summed over ranks (summarise_boundary reads
+    {"prediction": table}).  0 changes nothing."""
     import torch.distributed as dist
     from dasac_hip import ops
     core = net.module if hasattr(net, "module") else net
     was = core.training
     core.eval()
-    counts = None
+    counts, boundary, radius = None, None, int(boundary_radius)
     multi_scale = scales is not None or flip
     with torch.no_grad():
         for image, gt in batches:
@@ -480,20 +483,27 @@ def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confus
                     counts, _ = ops.confusion_counts([], [maps], gt, counts, num_classes=num_classes)
                 else:
                     counts = ops.mask_counts([], [maps.to(torch.int64)], gt, counts, num_classes=num_classes)
+                if radius > 0:
+                    boundary = ops.boundary_counts([], [maps], gt, boundary, radius, num_classes=num_classes)
             else:
                 _, logits_up = core(image)
                 if confusion:
                     counts, _ = ops.confusion_counts([logits_up], [], gt, counts)
                 else:
                     counts = ops.iou_counts(logits_up, gt, counts)
+                if radius > 0:
+                    boundary = ops.boundary_counts([logits_up], [], gt, boundary, radius)
     core.train(was)
     if (multi_scale or confusion) and counts is not None:
         counts = counts[0]
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(counts)
+        if boundary is not None:
+            dist.all_reduce(boundary)
     matrix = counts.cpu() if confusion else None
     iou, _, _ = summarise_iou(counts_from_confusion(matrix) if confusion else counts)
-    return (float(iou.mean()), iou, matrix) if confusion else (float(iou.mean()), iou)
+    result = (float(iou.mean()), iou, matrix) if confusion else (float(iou.mean()), iou)
+    return result + (boundary[0].cpu(),) if radius > 0 and boundary is not None else result
 
 
 def summarise_iou(counts):
@@ -598,6 +608,73 @@ def format_confusion(matrix, names):
     lines = [" ".join(["gt \\ pred".ljust(head)] + [n[:width].rjust(width) for n in names])]
     for n, row in zip(names, M.tolist()):
         lines.append(" ".join([n.ljust(head)] + [str(v).rjust(width) for v in row]))
+    return "\n".join(lines)
+
+
+def summarise_boundary(tables, ignore_classes=(), radii=(1, 2, 4, 8)):
+    """Reading of boundary tables (`validation(..., boundary_radius=R).boundary`: {layer: int64 [R+1,5,C]}, host or device; include/
+    dasac_hip.h: dasac_boundary_counts).  Slot s < R of a table holds the pixels at Chebyshev distance s + 1 from a class contour, slot
+    R everything further; the rows are tp, fp, fn (by the pixel's distance in the ground truth), pred (by its distance in the predicted
+    map) and both.  Returns {layer: {r: dict}} for every r of `radii` (a radius above R is a ValueError), each dict with
+      band_iou, band_miou            per-class IoU float32 [C] of the pixels within r of a ground-truth contour (the trimap band:
+                                     slots < r of tp, fp, fn), and its mean over the classes not in `ignore_classes`;
+      interior_iou, interior_miou    the same of all other pixels (slots >= r);
+      boundary_iou, boundary_miou    Boundary IoU (Cheng et al., 2021): I / (G + P - I) with G = sum (tp + fn), P = sum pred, I = sum both
+                                     over the slots < r -- the band inside the ground-truth mask against the band inside the predicted one;
+      error_share                    of all fp + fn of the classes not ignored, the share inside the band (0 without any error);
+      pixel_share                    of the pixels whose ground truth is such a class, the share inside the band.
+    Ratios follow summarise_iou: float32, numerator / max(1e-3, denominator), so a class without a pixel scores 0; means are
+    class_subset_mean; the two shares are python floats."""
+    import numpy as np
+    radii = [int(r) for r in radii]
+    ignore = set(int(i) for i in ignore_classes)
+    floor = torch.tensor(1e-3)
+    out = {}
+    for layer, table in tables.items():
+        T = table.detach().cpu().numpy().astype(np.int64)             # small host tables: integer bookkeeping in numpy
+        R, C = T.shape[0] - 1, T.shape[2]
+        if any(r < 1 or r > R for r in radii):
+            raise ValueError("summarise_boundary: radii {} for a table of radius {} (1..{} can be read from it)".format(radii, R, R))
+        keep = [c for c in range(C) if c not in ignore]
+        total = T.sum(0)
+        out[layer] = {}
+        for r in radii:
+            band = T[:r].sum(0)
+            inner = total - band
+            G, P, I = (torch.from_numpy(v).to(torch.float32) for v in (band[0] + band[2], band[3], band[4]))
+            rows = dict(band_iou=summarise_iou([torch.from_numpy(v) for v in band[:3]])[0],
+                        interior_iou=summarise_iou([torch.from_numpy(v) for v in inner[:3]])[0],
+                        boundary_iou=I / torch.maximum(floor, G + P - I))
+            entry = {}
+            for key, values in rows.items():
+                entry[key] = values
+                entry[key.replace("_iou", "_miou")] = class_subset_mean(values, ignore_classes)
+            errors, pixels = int((total[1] + total[2])[keep].sum()), int((total[0] + total[2])[keep].sum())
+            entry["error_share"] = int((band[1] + band[2])[keep].sum()) / errors if errors else 0.0
+            entry["pixel_share"] = int((band[0] + band[2])[keep].sum()) / pixels if pixels else 0.0
+            out[layer][r] = entry
+    return out
+
+
+def format_boundary(summary, names):
+    """Fixed-width text of a `summarise_boundary` result for the log: per layer one line per radius with the three means and the
+    two shares, then one row per class (`names`, C of them) with band / interior / Boundary IoU at every radius."""
+    names = [str(n) for n in names]
+    head = max(len("class"), max(len(n) for n in names))
+    lines = []
+    for layer, by_radius in summary.items():
+        radii = sorted(by_radius)
+        lines.append("{}: boundary bands".format(layer))
+        for r in radii:
+            e = by_radius[r]
+            assert len(names) == len(e["band_iou"]), (len(names), len(e["band_iou"]))
+            lines.append("  r={:<2d} band mIoU {:.4f}  interior mIoU {:.4f}  boundary mIoU {:.4f}  errors in band {:.4f}  pixels in band {:.4f}".format(
+                r, e["band_miou"], e["interior_miou"], e["boundary_miou"], e["error_share"], e["pixel_share"]))
+        lines.append(" ".join(["class".ljust(head)] + ["band@{0} intr@{0} bIoU@{0}".format(r).rjust(23) for r in radii]))
+        for c, n in enumerate(names):
+            lines.append(" ".join([n.ljust(head)] + ["{:.4f}  {:.4f}  {:.4f}".format(
+                float(by_radius[r]["band_iou"][c]), float(by_radius[r]["interior_iou"][c]), float(by_radius[r]["boundary_iou"][c])).rjust(23)
+                for r in radii]))
     return "\n".join(lines)
 
 
@@ -1059,7 +1136,7 @@ def summarise_validation(counts, ignore_classes=()):
 
 
 def validation(net, loader, step="source", group_size=None, max_iter=None, ignore_classes=(), num_classes=19, num_groups=None,
-               confusion=False, reliability_bins=0, consistency=False, consistency_cover=0.5):
+               confusion=False, reliability_bins=0, consistency=False, consistency_cover=0.5, boundary_radius=0):
     """`Trainer.validation` (train.py:339-469) with its step function (`step` :119-155 or `_step_target` :211-250, train=False):
     eval mode under no_grad (the previous mode is restored), loss means, one (tp, fp, fn) table per mask layer, the per-class and
     class-subset summaries and the checkpoint score.  Neither the teacher nor the class prior is updated.
@@ -1098,7 +1175,14 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     and accumulator afterwards.  The namespace's `consistency` is {"agree": int64 [C+1,T+1,T+1], "flips": [C,C], "per_view":
     [T,2]} on the host, summed over ranks as `table` is (one buffer, one collective, one copy), and `consistency_summary` is
     summarise_consistency of it (format_consistency renders it); {} and None when off.  Reported only: no other field, the
-    checkpoint score included, depends on it."""
+    checkpoint score included, depends on it.
+
+    Where in the image the errors are, opt-in: with `boundary_radius` R > 0 (at most ops.BOUNDARY_MAX_RADIUS) one
+    ops.boundary_counts per batch runs beside the count pass on the same layers into one device table, which is summed over ranks
+    as `table` is and copied once.  The namespace's `boundary` is {layer: int64 [R+1,5,C]} on the host (slot = Chebyshev distance to
+    the nearest class contour - 1, the last slot everything further; rows tp, fp, fn, pred, both) and `boundary_summary` is
+    summarise_boundary of it at the radii 1, 2, 4, ... up to R: trimap-band, interior and Boundary IoU per class and layer
+    (format_boundary renders it); {} and None when off.  Reported only: every other field is the one of a run without it."""
     from types import SimpleNamespace
     import torch.distributed as dist
     from dasac_hip import ops
@@ -1115,6 +1199,7 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     joint, bins = bool(confusion) or int(reliability_bins) > 0, int(reliability_bins)
     layers, table, rows, keys, matrices, rel = None, None, [], None, None, None
     cons, cons_was = None, None
+    radius, bound = int(boundary_radius), None
     if consistency:
         cons_was = core.swap_consistency((True, consistency_cover, None))
     try:
@@ -1146,6 +1231,8 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
                     ops.confusion_counts(scores, maps, gt, matrices, rel, logits_layers=logits)
                 else:
                     table = ops.mask_counts(scores, maps, gt, table, num_classes=num_classes)
+                if radius > 0:
+                    bound = ops.boundary_counts(scores, maps, gt, bound, radius, num_classes=num_classes)
                 rows.append(torch.cat([losses[k].detach().mean().reshape(1) for k in keys]))
     finally:
         core.train(was)
@@ -1153,7 +1240,7 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
             cons = core.swap_consistency(cons_was)[2]
     if table is None:
         return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0, confusion={}, reliability={},
-                               consistency={}, consistency_summary=None)
+                               consistency={}, consistency_summary=None, boundary={}, boundary_summary=None)
     if consistency and cons is None:        # a rank that owns no group (views sharded over ranks) still takes part in the sum
         cons = ops.consistency_tables(num_classes, group_size, device)
     names = layers[0] + layers[1]
@@ -1172,7 +1259,16 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
             if dist.get_backend() == "gloo":
                 cons = cons.cpu()
             dist.all_reduce(cons.buffer)
+        if bound is not None:
+            if dist.get_backend() == "gloo":
+                bound = bound.cpu()
+            dist.all_reduce(bound)
     table, loss_rows = table.cpu(), loss_rows.cpu().tolist()
+    bound_tables, bound_summary = {}, None
+    if bound is not None:
+        bound = bound.cpu()
+        bound_tables = {name: bound[i] for i, name in enumerate(names)}
+        bound_summary = summarise_boundary(bound_tables, ignore_classes, [r for r in (1, 2, 4, 8, 16) if r <= radius])
     cons_tables, cons_summary = {}, None
     if consistency:
         cons = cons.cpu()
@@ -1191,7 +1287,8 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     per_class, mean, score = summarise_validation(counts, ignore_classes)
     losses = {k: stat_mean([row[i] for row in loss_rows]) for i, k in enumerate(keys)}
     return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score,
-                           confusion=conf_tables, reliability=rel_tables, consistency=cons_tables, consistency_summary=cons_summary)
+                           confusion=conf_tables, reliability=rel_tables, consistency=cons_tables, consistency_summary=cons_summary,
+                           boundary=bound_tables, boundary_summary=bound_summary)
 
 
 # --------------------------------------------------------------------------------------------------

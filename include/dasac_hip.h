@@ -638,6 +638,41 @@ int dasac_confusion_counts(const float* scores0, const float* scores1, const flo
 int dasac_view_consistency(const float* aligned, int N, int T, int C, int64_t HW, float cover, int64_t* agree, int64_t* flips,
                            int64_t* per_view, dasac_stream_t stream);
 
+/* Where in the image the errors are: dasac_mask_counts' counts split by the distance to the nearest class contour -- trimap /
+ * boundary-band IoU, interior IoU and Boundary IoU (Cheng et al., 2021) follow from the tables; a diagnostic the reference does not
+ * have.  The layer slots are those of dasac_confusion_counts: up to 4 score tensors fp32 [B,C,H,W] (arg-max, first maximum wins), up
+ * to 2 label maps [B,H,W], int64 or, with bit i of `labels_u8_mask` set for slot labels<i>, uint8 at any address; NULL slots skipped,
+ * layers numbered over the non-NULL slots, scores first.  gt: int64 [B,H,W].
+ *   A MAP is one label per pixel (the ground truth, a label map, the arg-max of a score tensor).  Its class index is the value itself
+ *   when that lies in [0, C); every other value (255, -1, anything out of range) is "no class".  For a pixel p that holds a class,
+ *   d_L(p) is the smallest Chebyshev distance max(|dy|, |dx|) to a pixel q of the SAME image, inside it, that holds a DIFFERENT
+ *   class: no-class pixels are transparent (never a contour, never the cause of one), the image border is no contour, the images of
+ *   a batch do not see each other.  Equivalently d_L(p) <= r exactly when the class pixels of the (2r+1)^2 window around p are not all
+ *   of one class.  slot_L(p) = d_L(p) - 1 when 1 <= d_L(p) <= R, and R otherwise (further than R, no other class in reach, or p holds
+ *   no class).
+ *   table: int64 [L][R+1][5][C], ACCUMULATED into.  A pixel with gt == ignore_index is skipped for every row, and that is checked
+ *   first.  With g the ground truth, a the prediction, sg / sa the pixel's slot in the ground-truth map / in the predicted map:
+ *     row 0 tp, 1 fp, 2 fn   exactly dasac_mask_counts' rule (a == g adds tp[g] when g is a class; otherwise fp[a] when a is a
+ *                            class and fn[g] when g is a class), at slot sg;
+ *     row 3 pred             +1 at class a when a is a class, at slot sa;
+ *     row 4 both             +1 at class a when a == g is a class, at slot max(sg, sa).
+ *   The predicted map's distances are taken over the whole map, ignored pixels included as neighbours; only the counting skips
+ *   them.  Summed over the slots the rows are dasac_mask_counts' tp, fp, fn, tp + fp and tp bit for bit; the band of width r is the
+ *   slots < r, the interior the slots >= r, and Boundary IoU of class c at radius r is I / (G + P - I) with G = sum (tp + fn),
+ *   P = sum pred, I = sum both over the slots < r.
+ * 1 <= R <= DASAC_BOUNDARY_MAX_RADIUS, 1 <= C <= 64, B, H, W >= 1 with any alignment; offsets are 64-bit.  gt, table and the
+ * workspace are non-NULL, at least one layer is; fp32 / int64 tensors are aligned to their element size, the workspace to 16
+ * bytes and holds dasac_boundary_counts_workspace(layers, B, H, W) bytes (`layers` = the non-NULL slots; one uint8 map each and one
+ * for the ground truth -- an upper bound, since a uint8 label map is staged from where it is and the call asks for no map for it).
+ * Anything else is DASAC_EINVAL before any launch.  Integer adds only: exact, bit-identical from run to run and independent of tile order.  The
+ * scores are read once (arg-maxed into uint8 maps in the workspace, which the stencil then stages tile by tile with an R-wide
+ * halo); no load leaves a tensor.  Two launches on `stream`; no allocation, no synchronisation. */
+#define DASAC_BOUNDARY_MAX_RADIUS 16
+size_t dasac_boundary_counts_workspace(int layers, int B, int H, int W);
+int dasac_boundary_counts(const float* scores0, const float* scores1, const float* scores2, const float* scores3,
+                          const void* labels0, const void* labels1, int labels_u8_mask, const int64_t* gt, int B, int C, int H,
+                          int W, int R, int ignore_index, int64_t* table, void* workspace, size_t ws_bytes, dasac_stream_t stream);
+
 /* Per-image class statistics for importance-sampled target selection (tools/compute_IS_weights.py:58-83, on the device):
  * counts[b][v] += number of pixels of image b with value v, v in 0..255 (value 255 is counted too; callers drop it).
  * labels: [B][HW] uint8, any alignment (an unaligned head and a tail of any length per image are read byte by byte, the
