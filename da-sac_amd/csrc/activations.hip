@@ -39,12 +39,11 @@ struct ActTensor {      // one 32-byte row of `tensors`
 };
 static_assert(sizeof(ActTensor) == 32, "dasac_activation_stats: 32-byte descriptor rows");
 
-typedef float act_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 // activations are global memory; a pointer read from a descriptor row is a generic one to the compiler (flat loads) unless told.
 // A plane is addressed as "scalar plane base + 32-bit byte offset": planes of up to 2^30 floats, no 64-bit address per load.
 typedef const char __attribute__((address_space(1)))* act_gptr;
-__device__ __forceinline__ act_f32x4u act_load4(act_gptr plane, unsigned i) {
-  return *reinterpret_cast<const act_f32x4u __attribute__((address_space(1)))*>(plane + i * 4u);
+__device__ __forceinline__ f32x4u act_load4(act_gptr plane, unsigned i) {
+  return *reinterpret_cast<const f32x4u __attribute__((address_space(1)))*>(plane + i * 4u);
 }
 __device__ __forceinline__ float act_load1(act_gptr plane, unsigned i) {
   return *reinterpret_cast<const float __attribute__((address_space(1)))*>(plane + i * 4u);
@@ -79,7 +78,7 @@ __device__ __forceinline__ void act_take(ActAcc& a, float v, int i) {
   if (!fin) a.first = i < a.first ? i : a.first;
 }
 
-__device__ __forceinline__ void act_take4(ActAcc& a, act_f32x4u v, int i) {
+__device__ __forceinline__ void act_take4(ActAcc& a, f32x4u v, int i) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) act_take(a, v[e], i + e);
 }
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(kActBlock) void activation_stats_planes(const ActTe
     const int n = (int)HW, quads = n >> 2;
     int q = threadIdx.x;
     for (; q + 3 * kActBlock < quads; q += 4 * kActBlock) {      // four quads in flight
-      act_f32x4u v[4];
+      f32x4u v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = act_load4(x, 4 * (q + u * kActBlock));
 #pragma unroll

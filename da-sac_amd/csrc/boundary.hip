@@ -35,13 +35,14 @@
 // LDS: dynamic, sized by R and C: histogram + row table (32 + 2R) x 64 dwords + staged bytes (32 + 2R) x (64 + 2R): 19 KB at
 // R = 8, C = 19; 43 KB at the limits R = 16, C = 64.  Registers: eight pixels per thread (ground-truth code and slot each); C = 19
 // is compiled into the arg-max.  No scratch, <= 128 VGPRs.
-#include "common.hpp"
+#include "count_split.hpp"
+#include "count_stream.hpp"
 
 namespace dasac {
 
-constexpr int kBdBlock = 256;
+constexpr int kBdBlock = kCountBlock;
 constexpr int kBdWaves = kBdBlock / kWave;
-constexpr int kBdScores = 4, kBdMaps = 2, kBdLayers = kBdScores + kBdMaps;
+constexpr int kBdScores = kCountScores, kBdMaps = kCountMaps, kBdLayers = kBdScores + kBdMaps;
 constexpr int kBdMaxRadius = DASAC_BOUNDARY_MAX_RADIUS;
 constexpr int kBdMaxC = 64;
 constexpr int kBdRowsOut = 5;                          // tp, fp, fn, pred, both
@@ -52,55 +53,21 @@ constexpr int kBdIgnored = 0x80;                       // ground-truth code: the
 constexpr int kBdStage = 8;                            // byte loads a thread keeps in flight while it stages a tile
 constexpr int kBdBlocksPerCu = 8;
 
-typedef float bd_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef long long bd_i64x2u __attribute__((ext_vector_type(2), aligned(8)));
-
-struct BdSources {                                     // by value: no device-side table
-  const float* s[kBdScores];                           // [B,C,HW] fp32, the first `ns` set; workspace map 1 + l
-  const int64_t* m[kBdMaps];                           // [B,HW] int64, the first `nm` set
-  int m_dst[kBdMaps];                                  // ... and the workspace map each one goes to
-};
-
 struct BdMapSet {                                      // by value; [0] = ground-truth codes, [1 + l] = layer l
   const uint8_t* p[1 + kBdLayers];
   int64_t image_stride[1 + kBdLayers];                 // bytes from one image to the next
 };
 
-// four int64 labels at pixels r .. r+nx-1 as class codes; the slots past nx read as "no class"
-__device__ __forceinline__ void bd_load_labels(const int64_t* __restrict__ src, int nx, int64_t (&g)[4]) {
-  if (nx == 4) {
-    const bd_i64x2u a = *reinterpret_cast<const bd_i64x2u*>(src), b = *reinterpret_cast<const bd_i64x2u*>(src + 2);
-    g[0] = a[0];
-    g[1] = a[1];
-    g[2] = b[0];
-    g[3] = b[1];
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) g[e] = -1;
-#pragma unroll
-    for (int e = 0; e < 3; ++e)
-      if (e < nx) g[e] = src[e];
-  }
-}
-
-__device__ __forceinline__ bd_f32x4u bd_load_scores(const float* __restrict__ p, int nx) {
-  if (nx == 4) return *reinterpret_cast<const bd_f32x4u*>(p);
-  bd_f32x4u v = bd_f32x4u{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int e = 0; e < 3; ++e)
-    if (e < nx) v[e] = p[e];
-  return v;
-}
-
-// arg-max (first maximum wins, strict >) over the C planes at nx pixels from `lp` on, as four code bytes
+// arg-max (first maximum wins, strict >) over the C planes at nx pixels from `lp` on, as four code bytes.  Not argmax_quad: a running
+// maximum at every C -- with its 19 quads held at once beside the maps' codes this kernel takes 149 VGPRs instead of 95
 template <int CT>
 __device__ __forceinline__ unsigned bd_argmax4(const float* __restrict__ lp, int C, int64_t HW, int nx) {
-  bd_f32x4u best = bd_load_scores(lp, nx);
+  f32x4u best = load_quad(lp, nx);
   int arg[4] = {0, 0, 0, 0};
   if constexpr (CT > 0) {
 #pragma unroll
     for (int c = 1; c < CT; ++c) {
-      const bd_f32x4u v = bd_load_scores(lp + (int64_t)c * HW, nx);
+      const f32x4u v = load_quad(lp + (int64_t)c * HW, nx);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (v[e] > best[e]) {
@@ -110,7 +77,7 @@ __device__ __forceinline__ unsigned bd_argmax4(const float* __restrict__ lp, int
     }
   } else {
     for (int c = 1; c < C; ++c) {
-      const bd_f32x4u v = bd_load_scores(lp + (int64_t)c * HW, nx);
+      const f32x4u v = load_quad(lp + (int64_t)c * HW, nx);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (v[e] > best[e]) {
@@ -126,9 +93,10 @@ __device__ __forceinline__ unsigned bd_argmax4(const float* __restrict__ lp, int
 }
 
 // grid: B * blocks_per_image blocks; block (b, j) takes quads [j * per, (j + 1) * per) of image b (quad = 4 consecutive pixels).
-// ws: maps of `map_stride` bytes, images `HWp` (a multiple of 4) bytes apart: a quad is one aligned dword, also the last of an image
+// ws: maps of `map_stride` bytes (0 the ground truth, 1 + l score layer l, 1 + ns + l int64 map l), images `HWp` (a multiple of 4) bytes
+// apart: a quad is one aligned dword, also the last of an image
 template <int CT>
-__global__ __launch_bounds__(kBdBlock) void boundary_prepare(const BdSources src, int ns, int nm, const int64_t* __restrict__ gt,
+__global__ __launch_bounds__(kBdBlock) void boundary_prepare(const CountLayers src, int ns, int nm, const int64_t* __restrict__ gt,
                                                              int Crt, int64_t HW, int64_t HWp, int64_t map_stride,
                                                              int blocks_per_image, int64_t per, int64_t ignore_index,
                                                              uint8_t* __restrict__ ws) {
@@ -145,7 +113,7 @@ __global__ __launch_bounds__(kBdBlock) void boundary_prepare(const BdSources src
     const int nx = HW - r >= 4 ? 4 : (int)(HW - r);    // 1..4: r < HW because q < ceil(HW / 4)
     uint8_t* out = ws + b * HWp + r;                   // r + 4 <= HWp
     int64_t g[4];
-    bd_load_labels(gt + b * HW + r, nx, g);
+    load_quad(gt + b * HW + r, nx, -1, g);             // past nx: no class
     unsigned code = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -161,18 +129,18 @@ __global__ __launch_bounds__(kBdBlock) void boundary_prepare(const BdSources src
 #pragma unroll
     for (int l = 0; l < kBdMaps; ++l)
       if (l < nm) {
-        bd_load_labels(src.m[l] + b * HW + r, nx, g);
+        load_quad(static_cast<const int64_t*>(src.m[l]) + b * HW + r, nx, -1, g);
         code = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) code |= ((g[e] >= 0 && g[e] < C) ? (unsigned)g[e] : (unsigned)kBdNone) << (8 * e);
-        *reinterpret_cast<unsigned*>(out + src.m_dst[l] * map_stride) = code;
+        *reinterpret_cast<unsigned*>(out + (1 + ns + l) * map_stride) = code;
       }
   }
 }
 
 // one key per lane into the block's histogram; a negative key adds nothing.  A wave is one row of the tile: in an interior all its
 // lanes hold ONE key, which one lane adds for all (64 adds at one address would take 64 LDS cycles); next to a contour the keys
-// differ from lane to lane and every lane adds its own -- cheaper there than one round of the match loop of mc_add4 per key
+// differ from lane to lane and every lane adds its own -- cheaper there than one round of the match loop of count_add4 per key
 __device__ __forceinline__ void bd_add(unsigned int* __restrict__ h, int key) {
   if (key >= 0) {
     const int lead = __builtin_amdgcn_readfirstlane(key);
@@ -349,57 +317,47 @@ extern "C" int dasac_boundary_counts(const float* scores0, const float* scores1,
   DASAC_REQUIRE(B > 0 && H > 0 && W > 0, "boundary_counts: B, H and W must be positive");
   DASAC_REQUIRE(C >= 1 && C <= kBdMaxC, "boundary_counts: C must be in 1..%d", kBdMaxC);
   DASAC_REQUIRE(R >= 1 && R <= kBdMaxRadius, "boundary_counts: R must be in 1..%d", kBdMaxRadius);
-  BdSources src = {};
+  CountLayers src;
   BdMapSet maps = {};
   const int64_t HW = (int64_t)H * W, HWp = bd_image_bytes(H, W), map_stride = bd_map_bytes(B, H, W);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
-  const float* sc[kBdScores] = {scores0, scores1, scores2, scores3};
-  const void* mp[kBdMaps] = {labels0, labels1};
-  int ns = 0, nm = 0, n_layers = 0, n_ws = 1;          // workspace map 0 is the ground truth
-  bool aligned = (reinterpret_cast<uintptr_t>(gt) & 7u) == 0 && (reinterpret_cast<uintptr_t>(table) & 7u) == 0 &&
-                 (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0;
-  maps.p[0] = ws;
-  maps.image_stride[0] = HWp;
-  for (int i = 0; i < kBdScores; ++i)
-    if (sc[i]) {
-      aligned = aligned && (reinterpret_cast<uintptr_t>(sc[i]) & 3u) == 0;
-      src.s[ns++] = sc[i];
-      maps.p[1 + n_layers] = ws + n_ws++ * map_stride;
-      maps.image_stride[1 + n_layers++] = HWp;
+  int ns, nm;
+  const bool aligned = gather_count_layers(scores0, scores1, scores2, scores3, labels0, labels1, labels_u8_mask, src, ns, nm) &&
+                       ((reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(table)) & 7u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0;
+  int n_maps = 0, n_ws = 0, n64 = 0;
+  auto add_map = [&](const uint8_t* p, int64_t image_stride) {
+    maps.p[n_maps] = p;
+    maps.image_stride[n_maps++] = image_stride;
+  };
+  add_map(ws + n_ws++ * map_stride, HWp);              // workspace map 0 is the ground truth, 1 + l score layer l
+  for (int l = 0; l < ns; ++l) add_map(ws + n_ws++ * map_stride, HWp);
+  for (int l = 0; l < nm; ++l)
+    if (src.u8[l]) {                                   // staged from where it is, any address
+      add_map(static_cast<const uint8_t*>(src.m[l]), HW);
+    } else {                                           // boundary_prepare sees the int64 maps alone: map n64 to workspace map 1 + ns + n64
+      src.m[n64++] = src.m[l];
+      add_map(ws + n_ws++ * map_stride, HWp);
     }
-  for (int i = 0; i < kBdMaps; ++i)
-    if (mp[i]) {
-      if ((labels_u8_mask >> i) & 1) {                 // staged from where it is, any address
-        maps.p[1 + n_layers] = static_cast<const uint8_t*>(mp[i]);
-        maps.image_stride[1 + n_layers++] = HW;
-      } else {
-        aligned = aligned && (reinterpret_cast<uintptr_t>(mp[i]) & 7u) == 0;
-        src.m[nm] = static_cast<const int64_t*>(mp[i]);
-        src.m_dst[nm++] = n_ws;
-        maps.p[1 + n_layers] = ws + n_ws++ * map_stride;
-        maps.image_stride[1 + n_layers++] = HWp;
-      }
-    }
+  nm = n64;
+  const int n_layers = n_maps - 1;
   DASAC_REQUIRE(n_layers > 0, "boundary_counts: no layer");
   DASAC_REQUIRE(aligned, "boundary_counts: fp32 / int64 tensors must be aligned to their element size, the workspace to 16 bytes");
   DASAC_REQUIRE(ws_bytes >= (size_t)n_ws * (size_t)map_stride, "boundary_counts: workspace too small (%zu < %zu)", ws_bytes,
                 (size_t)n_ws * (size_t)map_stride);
   const int tiles_x = (W + kBdTileW - 1) / kBdTileW, tiles_y = (H + kBdTileH - 1) / kBdTileH;
   DASAC_REQUIRE((int64_t)tiles_x * tiles_y * B <= 0x7fffffffll, "boundary_counts: B * H * W too large for one launch");
-  // blocks per image of the streaming pass as in dasac_mask_counts
-  const int64_t n_quads = (HW + 3) >> 2;
-  int64_t bpi = (n_quads + 4 * kBdBlock - 1) / (4 * kBdBlock);
-  const int64_t fill = ((int64_t)(kNumCu - reserved_cus()) * kBdBlocksPerCu + B - 1) / B;
-  if (bpi > fill) bpi = fill;
+  // the streaming pass keeps no u32 bins: no limit on a block's quads
+  const QuadSplit split = quad_split((HW + 3) >> 2, B, kNumCu - reserved_cus(), kBdBlocksPerCu, 4, kBdBlock);
+  const int64_t bpi = split.blocks_per_image, per = split.quads_per_block;
   DASAC_REQUIRE(bpi * B <= 0x7fffffffll, "boundary_counts: B * H * W too large for one launch");
-  const int64_t per = (n_quads + bpi - 1) / bpi;
   hipStream_t s = as_stream(stream);
   if (C == 19) {
-    hipLaunchKernelGGL((boundary_prepare<19>), dim3((unsigned)(bpi * B)), dim3(kBdBlock), 0, s, src, ns, nm, gt, C, HW, HWp, map_stride,
-                       (int)bpi, per, (int64_t)ignore_index, ws);
+    hipLaunchKernelGGL((boundary_prepare<19>), dim3((unsigned)(bpi * B)), dim3(kBdBlock), 0, s, src, ns, nm, gt, C, HW, HWp,
+                       map_stride, (int)bpi, per, (int64_t)ignore_index, ws);
   } else {
-    hipLaunchKernelGGL((boundary_prepare<0>), dim3((unsigned)(bpi * B)), dim3(kBdBlock), 0, s, src, ns, nm, gt, C, HW, HWp, map_stride,
-                       (int)bpi, per, (int64_t)ignore_index, ws);
+    hipLaunchKernelGGL((boundary_prepare<0>), dim3((unsigned)(bpi * B)), dim3(kBdBlock), 0, s, src, ns, nm, gt, C, HW, HWp,
+                       map_stride, (int)bpi, per, (int64_t)ignore_index, ws);
   }
   DASAC_CHECK_LAUNCH("boundary_prepare");
   hipLaunchKernelGGL(boundary_stencil, dim3((unsigned)(tiles_x * tiles_y * B)), dim3(kBdBlock), bd_lds_bytes(R, C), s, maps, n_layers, C,

@@ -41,6 +41,12 @@ inline hipStream_t as_stream(dasac_stream_t s) { return reinterpret_cast<hipStre
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// vectors aligned to their ELEMENT: the planes of a [B,C,H,W] tensor with an odd H*W (769 x 769) sit at every 4-byte phase, and
+// global memory takes such a load or store at full width
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+typedef long long i64x2u __attribute__((ext_vector_type(2), aligned(8)));
+
 // grid for a grid-stride streaming kernel: enough blocks to fill 256 CUs several times over
 inline int stream_grid(int64_t work_items, int block, int max_blocks = 0) {
   if (max_blocks <= 0) max_blocks = (kNumCu - reserved_cus()) * 16;

@@ -19,7 +19,7 @@
 // Counting: integers only -- u32 LDS histograms per wave, one u64 global add per non-zero bin per block: exact, the same bits on
 // every run.  A block takes at most 2^27 pixels, so a bin (a pixel adds up to 28 pairs at T = 8) stays below 2^32.  Label maps are
 // a few large regions where every view agrees, so keys are merged before LDS: a thread whose four pixels share one `agree` key
-// joins the wave-wide match of mc_add4 (validation.hip) -- one lane adds 4 x (lanes holding the key), and, when that key says
+// joins the wave-wide match of count_stream.hpp -- one lane adds 4 x (lanes holding the key), and, when that key says
 // m == k, the k(k-1)/2 agreeing pairs of all those pixels with ONE add at flips[c*][c*].  Elsewhere a pixel whose covered views
 // agree makes one flips add, and only a disagreeing pixel adds pair by pair.  per_view is kept in registers across the loop: the
 // counts are taken wave-wide (ballots), so they are scalar registers and need no reduction at the end -- one LDS add per wave.
@@ -27,18 +27,16 @@
 // Registers: C = 19 with T = 2 and T = 4 compiled in (the class loop in trips of a dozen loads: fully unrolled, all 76 loads are
 // hoisted and spill); the runtime path (T <= 8, C <= 32) packs a view's four arg-maxes into one register.  Every load is "scalar
 // plane base + 32-bit lane offset", which saves the 64-bit vector address per load in flight.  <= 128 VGPRs, four waves per SIMD.
-#include "common.hpp"
+#include "count_stream.hpp"
 
 namespace dasac {
 
-constexpr int kVcBlock = 256;                          // 4 waves, each with its own agree + flips histogram
+constexpr int kVcBlock = kCountBlock;                        // 4 waves, each with its own agree + flips histogram
 constexpr int kVcWaves = kVcBlock / kWave;
 constexpr int kVcMaxViews = DASAC_CONSISTENCY_MAX_VIEWS;
 constexpr int kVcMaxC = 32;
 constexpr int kVcBlocksPerCu = 2;                      // the grid aims at no fewer (profiles/view_consistency.md)
 constexpr int64_t kVcMaxBlockQuads = 1ll << 25;        // 2^27 pixels x 28 pairs < 2^32: a block's u32 bins can not overflow
-
-typedef float vc_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 // TM views of four pixels: running maximum, arg-max (PACK: the four pixels' classes in the bytes of one register) and coverage sum
 template <int TM, bool PACK>
@@ -83,9 +81,9 @@ __device__ __forceinline__ void vc_class(VcViews<TM, PACK>& s, const float* __re
   for (int t = 0; t < TM; ++t)
     if (t < T) {
       const VC_GLOBAL char* tp = vc_scalar(p + t * view_stride);
-      vc_f32x4u v = vc_f32x4u{0.f, 0.f, 0.f, 0.f};
+      f32x4u v = f32x4u{0.f, 0.f, 0.f, 0.f};
       if constexpr (FULL) {
-        v = *(const VC_GLOBAL vc_f32x4u*)(tp + off);
+        v = *(const VC_GLOBAL f32x4u*)(tp + off);
       } else {
         v[0] = *(const VC_GLOBAL float*)(tp + off);
         v[1] = *(const VC_GLOBAL float*)(tp + off1);
@@ -225,35 +223,16 @@ __global__ __launch_bounds__(kVcBlock) void view_consistency(const float* __rest
 
     const bool merged = key[1] == key[0] && key[2] == key[0] && key[3] == key[0] && key[0] >= 0;
     if (merged) {
-      // wave-wide match over the lanes that hold one key each: one add per distinct key, and one for its unanimous pairs
+      // one add per distinct key of the wave, and one for its unanimous pairs
+      bool leader;
+      const unsigned count = 4u * wave_match(key[0], leader);
       const unsigned pairs = mm[0] == kk[0] ? (unsigned)(kk[0] * (kk[0] - 1) / 2) : 0u;
-      bool pending = true;
-      while (pending) {
-        const int lead = __builtin_amdgcn_readfirstlane(key[0]);
-        const unsigned long long same = __ballot(key[0] == lead);
-        if (key[0] == lead) {
-          if (lane == __ffsll((long long)same) - 1) {
-            const unsigned count = 4u * (unsigned)__popcll(same);
-            atomicAdd(&ha[lead], count);
-            if (pairs) atomicAdd(&hf[s.carg[0] * C + s.carg[0]], count * pairs);
-          }
-          pending = false;
-        }
+      if (leader) {
+        atomicAdd(&ha[key[0]], count);
+        if (pairs) atomicAdd(&hf[s.carg[0] * C + s.carg[0]], count * pairs);
       }
     } else {
-      int cur = key[0];
-      unsigned run = 1;
-#pragma unroll
-      for (int e = 1; e < 4; ++e) {
-        if (key[e] == cur) {
-          ++run;
-        } else {
-          if (cur >= 0) atomicAdd(&ha[cur], run);
-          cur = key[e];
-          run = 1;
-        }
-      }
-      if (cur >= 0) atomicAdd(&ha[cur], run);
+      count_runs4(ha, key);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e)
@@ -280,14 +259,13 @@ __global__ __launch_bounds__(kVcBlock) void view_consistency(const float* __rest
     }
 
   __syncthreads();
-  for (int i = threadIdx.x; i < n_wave; i += kVcBlock) {
+  for (int i = threadIdx.x; i < n_wave; i += kVcBlock) {      // not flush_bins: agree and flips are one table here, two outside
     unsigned long long sum = 0;
 #pragma unroll
     for (int w = 0; w < kVcWaves; ++w) sum += s_vc[w * n_wave + i];
     if (sum) atomicAdd(i < n_agree ? &agree[i] : &flips[i - n_agree], sum);
   }
-  for (int i = threadIdx.x; i < 2 * T; i += kVcBlock)
-    if (hv[i]) atomicAdd(&per_view[i], (unsigned long long)hv[i]);
+  flush_bins(hv, 1, 0, 2 * T, per_view);
 }
 
 }  // namespace dasac

@@ -42,7 +42,6 @@ __device__ __forceinline__ float* at_off(float* base, unsigned byte_off) {
 // HBM-bound: 76 B written per pixel and output.  Four pixels per thread make every store a (4-byte aligned) dwordx4 and
 // let the pixels share their low-resolution taps: at the 8x factor of the backbone the four x positions touch at most
 // three low-res columns, so a class costs 6 L1/L2 loads per 4 pixels instead of 16.
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 template <int CT, bool SOFTMAX, bool NARROW>
 __global__ __launch_bounds__(kHB, (SOFTMAX && NARROW) ? 4 : 1) void upsample_softmax(const float* __restrict__ x, int Crt, int h, int w, int H, int W,
@@ -578,7 +577,6 @@ __host__ __device__ __forceinline__ void ce_taps(int j, float sw, int W, int w, 
   while (hi > lo && weight_to(hi, sw, w, j) == 0.f) --hi;
 }
 constexpr int kCW = 64;
-typedef long long i64x2u __attribute__((ext_vector_type(2), aligned(8)));
 template <int CT, int SPAN>
 __global__ __launch_bounds__(kCW, 2) void ce_bwd_rows_wave(const float* __restrict__ xup, const int64_t* __restrict__ y,
                                                        const float* __restrict__ cw, int B, int H, int W, int w, float sw, int mode,
@@ -745,7 +743,6 @@ __device__ __forceinline__ Sample make_sample(const float* __restrict__ th, int 
 // instructions their CU's address unit processes -- 130 us of gathers + 91 us of stores = warp_back's 220 -- not by bytes).  The
 // two taps of a source row sit in columns {pb, pb + 1}, pb = min(cx0, W - 2): one dwordx2 at (row, pb) holds both, and a select
 // per tap puts each into place (clamped columns included: cx0, cx1 are always pb or pb + 1).  W >= 2.
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 struct SampleP {
   unsigned a_top, a_bot;      // byte offsets of the two pairs
   bool hi0, hi1;              // tap column == pb + 1

@@ -77,7 +77,6 @@ __global__ __launch_bounds__(256) void channel_sums(const float* __restrict__ x,
 // argmax byte: bits 0-6 = position inside the window (kh*k + kw), bit 7 = (pooled value > 0) for windows up to 11 x 11 -- the
 // backward pass with the producer's ReLU folded in (`relu_mask`) then needs no read of the pooled tensor (a third of its bytes)
 constexpr int kPoolSignMaxK = 11;
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 template <int KT, int ST>
 __global__ __launch_bounds__(256) void maxpool_fwd(const float* __restrict__ x, int H, int W, int OH, int OW, int k_rt, int s_rt,
@@ -269,7 +268,6 @@ __global__ __launch_bounds__(256) void maxpool_bwd(const float* __restrict__ dy,
 //   * the two index divisions are multiplications (FastDiv).
 // Every pixel adds its candidate windows in the order the kernel above does (window rows ascending, columns ascending, from
 // +0), a window that does not exist or whose pooled value is not positive (ReLU bit) contributes +0: identical bits.
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 __global__ __launch_bounds__(256) void maxpool_bwd_3s2p1(const float* __restrict__ dy, const uint8_t* __restrict__ arg, int H, int W,
                                                          int OH, int OW, int relu_mask, float* __restrict__ dx, int items, int Hp,
                                                          int Wq, FastDiv div_wq, FastDiv div_hp) {

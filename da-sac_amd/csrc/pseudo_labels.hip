@@ -16,7 +16,6 @@ constexpr int kPlMaxC = 64;
 // FOUR consecutive pixels per thread: every class plane is one (4-byte aligned) dwordx4 load, and with the compile-time class
 // count CT (19: the reference's NUM_CLASSES; 0 = runtime count, loads four classes at a time) all of a thread's plane loads
 // are in flight together; max_conf leaves as one dwordx4 store, the four argmax bytes as one dword.
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 template <int CT>
 __global__ __launch_bounds__(kPlBlock) void pl_argmax_peaks(const float* __restrict__ probs, int Crt, int64_t HW,

@@ -28,7 +28,9 @@ __device__ __forceinline__ void hist_add16(unsigned int* __restrict__ h, const u
   const unsigned first = v.x & 255u;
   const bool uniform = v.x == first * 0x01010101u && v.y == v.x && v.z == v.x && v.w == v.x;
   if (uniform) {
-    // wave-wide match over the lanes that hold one value each: one add per distinct value
+    // wave-wide match over the lanes that hold one value each: one add per distinct value.  Its own loop and its own flush, not
+    // wave_match / flush_bins of count_stream.hpp: with the add behind the loop the compiler merges it with the walk's last add
+    // below, at 69 more instructions, and the 8 us rows did not hold the parent's time (profiles/count_stream_refactor.md)
     const int lane = (int)(threadIdx.x & (kWave - 1));
     bool pending = true;
     while (pending) {

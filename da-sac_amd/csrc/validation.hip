@@ -17,16 +17,9 @@
 // being exact past 2^24 pixels per class; the project keeps exact int64 counts and a float32 summary (driver.summarise_iou,
 // g14), here too.
 //
-// Streaming shape: lanes along pixels, four consecutive pixels per thread, every class plane ONE dwordx4 load.  The
-// planes of a [B,C,H,W] tensor with an odd H*W (769 x 769) sit at every 4-byte phase, so the loads are declared 4-byte aligned
-// (`aligned(4)` vector types, as in head.hip: global memory takes them at full width) -- no head to peel; the ground truth and
-// the label maps are two 8-byte-aligned 16-byte loads.  The last 1..3 pixels of an image are read element by element: no load
-// touches an element outside its own image, so none leaves a buffer.  A quad whose four pixels are all ignored skips its
-// score loads.
-//
-// Segmentation maps are a few large regions, the worst input of a one-atomic-per-pixel histogram.  Keys are merged before
-// LDS as in label_hist (sampling.hip): a thread whose four keys are equal joins a wave-wide match -- per distinct key ONE lane
-// adds 4 x (lanes holding it) -- every other thread adds once per run of equal keys.
+// Streaming shape, loaders and key merging: count_stream.hpp (a quad of four pixels per thread, one dwordx4 per class plane, the
+// last 1..3 pixels of an image element by element; count_add4 merges equal keys before LDS).  A quad whose four pixels are all
+// ignored skips its score loads.
 //
 // Registers: C = 19 is compiled in (19 x 4 values in flight per layer, layers one after the other): <= 128 VGPRs, four waves
 // per SIMD; the runtime-C path keeps a running maximum.
@@ -35,58 +28,17 @@
 // class x confidence bin x hit) -- a diagnostic the reference does not have; the marginal counts above follow from its tables.
 #include <atomic>
 
-#include "common.hpp"
+#include "count_split.hpp"
+#include "count_stream.hpp"
 
 namespace dasac {
 
-constexpr int kMcBlock = 256;                          // 4 waves, each with its own [layers][3][64] u32 histogram
+constexpr int kMcBlock = kCountBlock;                  // 4 waves, each with its own [layers][3][64] u32 histogram
 constexpr int kMcWaves = kMcBlock / kWave;
-constexpr int kMcScores = 4, kMcMaps = 2, kMcLayers = kMcScores + kMcMaps;
+constexpr int kMcScores = kCountScores, kMcMaps = kCountMaps, kMcLayers = kMcScores + kMcMaps;
 constexpr int kMcBins = 3 * 64;                        // key = kind * 64 + class, kind 0 tp / 1 fp / 2 fn
-constexpr int kMcNone = 255;                           // "adds nothing"
 constexpr int kMcBlocksPerCu = 8;
 constexpr int64_t kMcMaxBlockQuads = 1ll << 29;        // a block's u32 bins can not overflow: at most 2^31 pixels per block
-
-typedef float mc_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef long long mc_i64x2u __attribute__((ext_vector_type(2), aligned(8)));
-
-struct MaskLayers {                                    // by value: no device-side table
-  const float* s[kMcScores];                           // [B,C,HW] fp32, the first `ns` set
-  const int64_t* m[kMcMaps];                           // [B,HW] int64, the first `nm` set
-};
-
-// one thread's four keys of one kind into the wave's histogram of one layer
-__device__ __forceinline__ void mc_add4(unsigned int* __restrict__ h, const int (&k)[4]) {
-  if (k[1] == k[0] && k[2] == k[0] && k[3] == k[0]) {
-    if (k[0] != kMcNone) {
-      // wave-wide match over the lanes that hold one key each: one add per distinct key
-      const int lane = (int)(threadIdx.x & (kWave - 1));
-      bool pending = true;
-      while (pending) {
-        const int lead = __builtin_amdgcn_readfirstlane(k[0]);
-        const unsigned long long same = __ballot(k[0] == lead);
-        if (k[0] == lead) {
-          if (lane == __ffsll((long long)same) - 1) atomicAdd(&h[lead], 4u * (unsigned)__popcll(same));
-          pending = false;
-        }
-      }
-    }
-  } else {
-    int cur = k[0];
-    unsigned run = 1;
-#pragma unroll
-    for (int e = 1; e < 4; ++e) {
-      if (k[e] == cur) {
-        ++run;
-      } else {
-        if (cur != kMcNone) atomicAdd(&h[cur], run);
-        cur = k[e];
-        run = 1;
-      }
-    }
-    if (cur != kMcNone) atomicAdd(&h[cur], run);
-  }
-}
 
 // keys of one layer's four predictions: pc = predicted class or -1 when it is no class, eq = (p == g) on the full values
 __device__ __forceinline__ void mc_count(unsigned int* __restrict__ h, const int (&pc)[4], const bool (&eq)[4], const int (&gc)[4],
@@ -94,90 +46,23 @@ __device__ __forceinline__ void mc_count(unsigned int* __restrict__ h, const int
   int k1[4], k2[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    k1[e] = skip[e] ? kMcNone : eq[e] ? (gc[e] >= 0 ? gc[e] : kMcNone) : (pc[e] >= 0 ? 64 + pc[e] : kMcNone);
-    k2[e] = (skip[e] || eq[e] || gc[e] < 0) ? kMcNone : 128 + gc[e];
+    k1[e] = skip[e] ? -1 : eq[e] ? gc[e] : (pc[e] | 64);                  // a class is < 64: | adds the kind, and -1 stays -1
+    k2[e] = (skip[e] || eq[e]) ? -1 : (gc[e] | 128);
   }
-  mc_add4(h, k1);
-  mc_add4(h, k2);
+  count_add4(h, k1);
+  count_add4(h, k2);
 }
 
-// arg-max over the C planes of one score tensor at pixels r .. r+nx-1 of one image (`img` = the image's first plane)
-template <int CT>
-__device__ __forceinline__ void mc_argmax(const float* __restrict__ img, int C, int64_t HW, int64_t r, int nx, int (&p)[4]) {
-  const float* lp = img + r;
-  if constexpr (CT > 0) {
-    mc_f32x4u v[CT];
-    if (nx == 4) {
-#pragma unroll
-      for (int c = 0; c < CT; ++c) v[c] = *reinterpret_cast<const mc_f32x4u*>(lp + (int64_t)c * HW);
-    } else {
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        v[c] = mc_f32x4u{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-          if (e < nx) v[c][e] = lp[(int64_t)c * HW + e];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float best = v[0][e];
-      int k = 0;
-#pragma unroll
-      for (int c = 1; c < CT; ++c)
-        if (v[c][e] > best) {
-          best = v[c][e];
-          k = c;
-        }
-      p[e] = k;
-    }
-  } else {
-    float best[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      best[e] = e < nx ? lp[e] : 0.f;
-      p[e] = 0;
-    }
-    for (int c = 1; c < C; ++c) {
-      const float* cp = lp + (int64_t)c * HW;
-      mc_f32x4u v = mc_f32x4u{0.f, 0.f, 0.f, 0.f};
-      if (nx == 4) {
-        v = *reinterpret_cast<const mc_f32x4u*>(cp);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-          if (e < nx) v[e] = cp[e];
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (v[e] > best[e]) {
-          best[e] = v[e];
-          p[e] = c;
-        }
-    }
-  }
-}
-
-// four int64 labels at pixels r .. r+nx-1; the slots past nx read as `fill`
-__device__ __forceinline__ void mc_load_labels(const int64_t* __restrict__ src, int nx, int64_t fill, int64_t (&g)[4]) {
-  if (nx == 4) {
-    const mc_i64x2u a = *reinterpret_cast<const mc_i64x2u*>(src), b = *reinterpret_cast<const mc_i64x2u*>(src + 2);
-    g[0] = a[0];
-    g[1] = a[1];
-    g[2] = b[0];
-    g[3] = b[1];
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) g[e] = fill;
-#pragma unroll
-    for (int e = 0; e < 3; ++e)
-      if (e < nx) g[e] = src[e];
-  }
+// the launch's split of an image's quads over blocks (count_split.hpp), or the error when the grid does not fit one launch
+static int mc_split(const char* what, int64_t HW, int B, QuadSplit& split) {
+  split = quad_split((HW + 3) >> 2, B, kNumCu - reserved_cus(), kMcBlocksPerCu, 4, kMcBlock, kMcMaxBlockQuads);
+  DASAC_REQUIRE(split.blocks_per_image * B <= 0x7fffffffll, "%s: B * HW too large for one launch", what);
+  return DASAC_OK;
 }
 
 // grid: B * blocks_per_image blocks; block (b, j) takes quads [j * per, (j + 1) * per) of image b (quad = 4 consecutive pixels)
 template <int CT>
-__global__ __launch_bounds__(kMcBlock) void mask_counts(const MaskLayers layers, int ns, int nm, const int64_t* __restrict__ gt,
+__global__ __launch_bounds__(kMcBlock) void mask_counts(const CountLayers layers, int ns, int nm, const int64_t* __restrict__ gt,
                                                         int Crt, int64_t HW, int blocks_per_image, int64_t per,
                                                         int64_t ignore_index, unsigned long long* __restrict__ counts) {
   __shared__ unsigned int s[kMcWaves][kMcLayers * kMcBins];
@@ -198,7 +83,7 @@ __global__ __launch_bounds__(kMcBlock) void mask_counts(const MaskLayers layers,
     const int64_t r = q << 2;
     const int nx = HW - r >= 4 ? 4 : (int)(HW - r);    // 1..4: r < HW because q < ceil(HW / 4)
     int64_t g[4];
-    mc_load_labels(gt_b + r, nx, ignore_index, g);
+    load_quad(gt_b + r, nx, ignore_index, g);
     bool skip[4];
     int gc[4];
 #pragma unroll
@@ -211,7 +96,7 @@ __global__ __launch_bounds__(kMcBlock) void mask_counts(const MaskLayers layers,
     for (int l = 0; l < kMcScores; ++l)
       if (l < ns) {
         int pc[4];
-        mc_argmax<CT>(layers.s[l] + b * C * HW, C, HW, r, nx, pc);
+        argmax_quad<CT>(layers.s[l] + b * C * HW, C, HW, r, nx, pc);
         bool eq[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) eq[e] = g[e] == pc[e];
@@ -221,7 +106,7 @@ __global__ __launch_bounds__(kMcBlock) void mask_counts(const MaskLayers layers,
     for (int l = 0; l < kMcMaps; ++l)
       if (l < nm) {
         int64_t p[4];
-        mc_load_labels(layers.m[l] + b * HW + r, nx, ignore_index, p);
+        load_quad(static_cast<const int64_t*>(layers.m[l]) + b * HW + r, nx, ignore_index, p);
         int pc[4];
         bool eq[4];
 #pragma unroll
@@ -256,123 +141,9 @@ constexpr int kCfMaxBins = 32;
 constexpr size_t kCfLdsMax = 160 * 1024;               // what one workgroup may take
 constexpr size_t kCfLdsPlain = 64 * 1024;              // above this a kernel's dynamic-LDS limit has to be raised
 
-struct ConfusionLayers {                               // by value: no device-side table
-  const float* s[kMcScores];                           // [B,C,HW] fp32, the first `ns` set
-  const void* m[kMcMaps];                              // [B,HW] int64 or uint8, the first `nm` set
-  int u8[kMcMaps];                                     // map l holds uint8
-};
-
-// one thread's four keys into one table; a negative key adds nothing (mc_add4 with the sentinel out of the key space)
-__device__ __forceinline__ void cf_add4(unsigned int* __restrict__ h, const int (&k)[4]) {
-  if (k[1] == k[0] && k[2] == k[0] && k[3] == k[0]) {
-    if (k[0] >= 0) {
-      const int lane = (int)(threadIdx.x & (kWave - 1));
-      bool pending = true;
-      while (pending) {
-        const int lead = __builtin_amdgcn_readfirstlane(k[0]);
-        const unsigned long long same = __ballot(k[0] == lead);
-        if (k[0] == lead) {
-          if (lane == __ffsll((long long)same) - 1) atomicAdd(&h[lead], 4u * (unsigned)__popcll(same));
-          pending = false;
-        }
-      }
-    }
-  } else {
-    int cur = k[0];
-    unsigned run = 1;
-#pragma unroll
-    for (int e = 1; e < 4; ++e) {
-      if (k[e] == cur) {
-        ++run;
-      } else {
-        if (cur >= 0) atomicAdd(&h[cur], run);
-        cur = k[e];
-        run = 1;
-      }
-    }
-    if (cur >= 0) atomicAdd(&h[cur], run);
-  }
-}
-
-// mc_argmax that also returns the winning confidence: the winning score itself, or with `softmax` 1 / sum_c expf(x_c - max_c x)
-// (classes in order, fp32).  The runtime-C path reads the planes a second time for that sum.
-template <int CT>
-__device__ __forceinline__ void cf_argmax_conf(const float* __restrict__ img, int C, int64_t HW, int64_t r, int nx, bool softmax,
-                                               int (&p)[4], float (&conf)[4]) {
-  const float* lp = img + r;
-  if constexpr (CT > 0) {
-    mc_f32x4u v[CT];
-    if (nx == 4) {
-#pragma unroll
-      for (int c = 0; c < CT; ++c) v[c] = *reinterpret_cast<const mc_f32x4u*>(lp + (int64_t)c * HW);
-    } else {
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        v[c] = mc_f32x4u{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-          if (e < nx) v[c][e] = lp[(int64_t)c * HW + e];
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float best = v[0][e];
-      int k = 0;
-#pragma unroll
-      for (int c = 1; c < CT; ++c)
-        if (v[c][e] > best) {
-          best = v[c][e];
-          k = c;
-        }
-      p[e] = k;
-      conf[e] = best;
-    }
-    if (softmax) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < CT; ++c) sum += expf(v[c][e] - conf[e]);
-        conf[e] = 1.0f / sum;
-      }
-    }
-  } else {
-    mc_argmax<0>(img, C, HW, r, nx, p);
-    float best[4], sum[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      best[e] = e < nx ? lp[(int64_t)p[e] * HW + e] : 0.f;
-      sum[e] = 0.f;
-    }
-    if (softmax) {
-      for (int c = 0; c < C; ++c) {
-        const float* cp = lp + (int64_t)c * HW;
-        mc_f32x4u v = mc_f32x4u{0.f, 0.f, 0.f, 0.f};
-        if (nx == 4) {
-          v = *reinterpret_cast<const mc_f32x4u*>(cp);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 3; ++e)
-            if (e < nx) v[e] = cp[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sum[e] += expf(v[e] - best[e]);
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) conf[e] = softmax ? 1.0f / sum[e] : best[e];
-  }
-}
-
-// four uint8 labels at pixels r .. r+nx-1 (any address: byte loads); the slots past nx read as `fill`
-__device__ __forceinline__ void cf_load_labels_u8(const uint8_t* __restrict__ src, int nx, int64_t fill, int64_t (&g)[4]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) g[e] = e < nx ? (int64_t)src[e] : fill;
-}
-
 // grid and block as mask_counts; dynamic LDS: (copies * (ns + nm) * (C+1)^2 + (REL ? ns * C * n_bins * 2 : 0)) * 4 bytes
 template <int CT, bool REL>
-__global__ __launch_bounds__(kMcBlock) void confusion_counts(const ConfusionLayers layers, int ns, int nm,
+__global__ __launch_bounds__(kMcBlock) void confusion_counts(const CountLayers layers, int ns, int nm,
                                                              const int64_t* __restrict__ gt, int Crt, int64_t HW, int blocks_per_image,
                                                              int64_t per, int64_t ignore_index, int copies, int n_bins, int softmax_mask,
                                                              unsigned long long* __restrict__ confusion,
@@ -400,7 +171,7 @@ __global__ __launch_bounds__(kMcBlock) void confusion_counts(const ConfusionLaye
     const int64_t r = q << 2;
     const int nx = HW - r >= 4 ? 4 : (int)(HW - r);    // 1..4: r < HW because q < ceil(HW / 4)
     int64_t g[4];
-    mc_load_labels(gt_b + r, nx, ignore_index, g);
+    load_quad(gt_b + r, nx, ignore_index, g);
     bool skip[4];
     int row[4];                                        // the row's first bin
 #pragma unroll
@@ -415,7 +186,7 @@ __global__ __launch_bounds__(kMcBlock) void confusion_counts(const ConfusionLaye
         int pc[4], k[4];
         if constexpr (REL) {
           float conf[4];
-          cf_argmax_conf<CT>(layers.s[l] + b * C * HW, C, HW, r, nx, (softmax_mask >> l) & 1, pc, conf);
+          argmax_quad<CT, true>(layers.s[l] + b * C * HW, C, HW, r, nx, (softmax_mask >> l) & 1, pc, conf);
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (!skip[e]) {
@@ -424,38 +195,31 @@ __global__ __launch_bounds__(kMcBlock) void confusion_counts(const ConfusionLaye
               atomicAdd(&hr[((l * C + pc[e]) * n_bins + bin) * 2 + (row[e] == pc[e] * side ? 1 : 0)], 1u);
             }
         } else {
-          mc_argmax<CT>(layers.s[l] + b * C * HW, C, HW, r, nx, pc);
+          argmax_quad<CT>(layers.s[l] + b * C * HW, C, HW, r, nx, pc);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) k[e] = skip[e] ? -1 : row[e] + pc[e];
-        cf_add4(hw + l * bins, k);
+        count_add4(hw + l * bins, k);
       }
 #pragma unroll
     for (int l = 0; l < kMcMaps; ++l)
       if (l < nm) {
         int64_t p[4];
         if (layers.u8[l]) {
-          cf_load_labels_u8(static_cast<const uint8_t*>(layers.m[l]) + b * HW + r, nx, ignore_index, p);
+          load_quad(static_cast<const uint8_t*>(layers.m[l]) + b * HW + r, nx, ignore_index, p);
         } else {
-          mc_load_labels(static_cast<const int64_t*>(layers.m[l]) + b * HW + r, nx, ignore_index, p);
+          load_quad(static_cast<const int64_t*>(layers.m[l]) + b * HW + r, nx, ignore_index, p);
         }
         int k[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) k[e] = skip[e] ? -1 : row[e] + ((p[e] >= 0 && p[e] < C) ? (int)p[e] : C);
-        cf_add4(hw + (ns + l) * bins, k);
+        count_add4(hw + (ns + l) * bins, k);
       }
   }
 
   __syncthreads();
-  for (int i = threadIdx.x; i < n_conf; i += kMcBlock) {
-    unsigned long long sum = 0;
-    for (int w = 0; w < copies; ++w) sum += s_cf[w * n_conf + i];
-    if (sum) atomicAdd(&confusion[i], sum);
-  }
-  if constexpr (REL) {
-    for (int i = threadIdx.x; i < n_rel; i += kMcBlock)
-      if (hr[i]) atomicAdd(&reliability[i], (unsigned long long)hr[i]);
-  }
+  flush_bins(s_cf, copies, n_conf, n_conf, confusion);
+  if constexpr (REL) flush_bins(hr, 1, 0, n_rel, reliability);
 }
 
 inline size_t cf_lds_bytes(int copies, int layers, int scores, int C, int n_bins) {
@@ -463,7 +227,7 @@ inline size_t cf_lds_bytes(int copies, int layers, int scores, int C, int n_bins
 }
 
 // one launch over `ns` score layers and `nm` label maps (either may be 0) into tables that start at these layers
-static int cf_launch(const ConfusionLayers& layers, int ns, int nm, const int64_t* gt, int B, int C, int64_t HW, int ignore_index,
+static int cf_launch(const CountLayers& layers, int ns, int nm, const int64_t* gt, int B, int C, int64_t HW, int ignore_index,
                      int64_t* confusion, int64_t* reliability, int n_bins, int softmax_mask, hipStream_t stream) {
   const int rel_bins = reliability && ns > 0 ? n_bins : 0;
   const bool rel = rel_bins > 0;
@@ -483,21 +247,14 @@ static int cf_launch(const ConfusionLayers& layers, int ns, int nm, const int64_
       raised.fetch_or(bit, std::memory_order_relaxed);
     }
   }
-  // blocks per image as in dasac_mask_counts
-  const int64_t n_quads = (HW + 3) >> 2;
-  int64_t bpi = (n_quads + 4 * kMcBlock - 1) / (4 * kMcBlock);
-  const int64_t fill = ((int64_t)(kNumCu - reserved_cus()) * kMcBlocksPerCu + B - 1) / B;
-  if (bpi > fill) bpi = fill;
-  const int64_t need = (n_quads + kMcMaxBlockQuads - 1) / kMcMaxBlockQuads;
-  if (bpi < need) bpi = need;
-  DASAC_REQUIRE(bpi * B <= 0x7fffffffll, "confusion_counts: B * HW too large for one launch");
-  const int64_t per = (n_quads + bpi - 1) / bpi;
-  const dim3 grid((unsigned)(bpi * B)), block(kMcBlock);
+  QuadSplit split;
+  if (int rc = mc_split("confusion_counts", HW, B, split)) return rc;
+  const dim3 grid((unsigned)(split.blocks_per_image * B)), block(kMcBlock);
   unsigned long long* out = reinterpret_cast<unsigned long long*>(confusion);
   unsigned long long* out_rel = reinterpret_cast<unsigned long long*>(reliability);
 #define DASAC_CF_LAUNCH(CT, REL)                                                                                                  \
-  hipLaunchKernelGGL((confusion_counts<CT, REL>), grid, block, lds, stream, layers, ns, nm, gt, C, HW, (int)bpi, per,            \
-                     (int64_t)ignore_index, copies, rel_bins, softmax_mask, out, out_rel)
+  hipLaunchKernelGGL((confusion_counts<CT, REL>), grid, block, lds, stream, layers, ns, nm, gt, C, HW, (int)split.blocks_per_image,   \
+                     split.quads_per_block, (int64_t)ignore_index, copies, rel_bins, softmax_mask, out, out_rel)
   if (C == 19) {
     if (rel) DASAC_CF_LAUNCH(19, true); else DASAC_CF_LAUNCH(19, false);
   } else {
@@ -519,22 +276,12 @@ extern "C" int dasac_confusion_counts(const float* scores0, const float* scores1
   DASAC_REQUIRE(B > 0 && C > 0 && HW > 0, "confusion_counts: B, C and HW must be positive");
   DASAC_REQUIRE(C <= 64, "confusion_counts: at most 64 classes");
   DASAC_REQUIRE(!reliability || (n_bins >= 1 && n_bins <= kCfMaxBins), "confusion_counts: n_bins must be in 1..32");
-  ConfusionLayers layers = {};
-  int ns = 0, nm = 0;
-  const float* sc[kMcScores] = {scores0, scores1, scores2, scores3};
-  const void* mp[kMcMaps] = {labels0, labels1};
-  for (int i = 0; i < kMcScores; ++i)
-    if (sc[i]) layers.s[ns++] = sc[i];
-  for (int i = 0; i < kMcMaps; ++i)
-    if (mp[i]) {
-      layers.u8[nm] = (labels_u8_mask >> i) & 1;
-      layers.m[nm++] = mp[i];
-    }
+  CountLayers layers;
+  int ns, nm;
+  const bool aligned = gather_count_layers(scores0, scores1, scores2, scores3, labels0, labels1, labels_u8_mask, layers, ns, nm) &&
+                       ((reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(confusion) |
+                         reinterpret_cast<uintptr_t>(reliability)) & 7u) == 0;
   DASAC_REQUIRE(ns + nm > 0, "confusion_counts: no layer");
-  bool aligned = (reinterpret_cast<uintptr_t>(gt) & 7u) == 0 && (reinterpret_cast<uintptr_t>(confusion) & 7u) == 0 &&
-                 (reinterpret_cast<uintptr_t>(reliability) & 7u) == 0;
-  for (int i = 0; i < ns; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(layers.s[i]) & 3u) == 0;
-  for (int i = 0; i < nm; ++i) aligned = aligned && (layers.u8[i] || (reinterpret_cast<uintptr_t>(layers.m[i]) & 7u) == 0);
   DASAC_REQUIRE(aligned, "confusion_counts: fp32 / int64 tensors must be aligned to their element size");
   hipStream_t s = as_stream(stream);
   const int rel_bins = reliability && ns > 0 ? n_bins : 0;
@@ -544,7 +291,7 @@ extern "C" int dasac_confusion_counts(const float* scores0, const float* scores1
   // (with their reliability tables) and the label maps go in two launches
   int rc = cf_launch(layers, ns, 0, gt, B, C, HW, ignore_index, confusion, reliability, n_bins, softmax_mask, s);
   if (rc != DASAC_OK) return rc;
-  ConfusionLayers maps = {};
+  CountLayers maps = {};
   for (int i = 0; i < nm; ++i) {
     maps.m[i] = layers.m[i];
     maps.u8[i] = layers.u8[i];
@@ -559,36 +306,23 @@ extern "C" int dasac_mask_counts(const float* scores0, const float* scores1, con
   DASAC_REQUIRE(gt && counts, "mask_counts: null gt or counts");
   DASAC_REQUIRE(B > 0 && C > 0 && HW > 0, "mask_counts: B, C and HW must be positive");
   DASAC_REQUIRE(C <= 64, "mask_counts: at most 64 classes");
-  MaskLayers layers = {};
-  int ns = 0, nm = 0;
-  const float* sc[kMcScores] = {scores0, scores1, scores2, scores3};
-  const int64_t* mp[kMcMaps] = {labels0, labels1};
-  for (int i = 0; i < kMcScores; ++i)
-    if (sc[i]) layers.s[ns++] = sc[i];
-  for (int i = 0; i < kMcMaps; ++i)
-    if (mp[i]) layers.m[nm++] = mp[i];
+  CountLayers layers;
+  int ns, nm;
+  const bool aligned = gather_count_layers(scores0, scores1, scores2, scores3, labels0, labels1, 0, layers, ns, nm) &&
+                       ((reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(counts)) & 7u) == 0;
   DASAC_REQUIRE(ns + nm > 0, "mask_counts: no layer");
-  bool aligned = (reinterpret_cast<uintptr_t>(gt) & 7u) == 0 && (reinterpret_cast<uintptr_t>(counts) & 7u) == 0;
-  for (int i = 0; i < ns; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(layers.s[i]) & 3u) == 0;
-  for (int i = 0; i < nm; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(layers.m[i]) & 7u) == 0;
   DASAC_REQUIRE(aligned, "mask_counts: fp32 / int64 tensors must be aligned to their element size");
-  // blocks per image: at least four quads per thread until the grid holds kMcBlocksPerCu blocks per CU, and never fewer than
-  // keeps a block's pixel count at or below 2^31 (u32 bins)
-  const int64_t n_quads = (HW + 3) >> 2;
-  int64_t bpi = (n_quads + 4 * kMcBlock - 1) / (4 * kMcBlock);
-  const int64_t fill = ((int64_t)(kNumCu - reserved_cus()) * kMcBlocksPerCu + B - 1) / B;
-  if (bpi > fill) bpi = fill;
-  const int64_t need = (n_quads + kMcMaxBlockQuads - 1) / kMcMaxBlockQuads;
-  if (bpi < need) bpi = need;
-  DASAC_REQUIRE(bpi * B <= 0x7fffffffll, "mask_counts: B * HW too large for one launch");
-  const int64_t per = (n_quads + bpi - 1) / bpi;
-  const dim3 grid((unsigned)(bpi * B)), block(kMcBlock);
+  QuadSplit split;
+  if (int rc = mc_split("mask_counts", HW, B, split)) return rc;
+  const dim3 grid((unsigned)(split.blocks_per_image * B)), block(kMcBlock);
+  const int bpi = (int)split.blocks_per_image;
+  const int64_t per = split.quads_per_block;
   unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
   if (C == 19) {
-    hipLaunchKernelGGL((mask_counts<19>), grid, block, 0, as_stream(stream), layers, ns, nm, gt, C, HW, (int)bpi, per,
+    hipLaunchKernelGGL((mask_counts<19>), grid, block, 0, as_stream(stream), layers, ns, nm, gt, C, HW, bpi, per,
                        (int64_t)ignore_index, out);
   } else {
-    hipLaunchKernelGGL((mask_counts<0>), grid, block, 0, as_stream(stream), layers, ns, nm, gt, C, HW, (int)bpi, per,
+    hipLaunchKernelGGL((mask_counts<0>), grid, block, 0, as_stream(stream), layers, ns, nm, gt, C, HW, bpi, per,
                        (int64_t)ignore_index, out);
   }
   DASAC_CHECK_LAUNCH("mask_counts");

@@ -1225,38 +1225,58 @@ def label_hist(labels_u8, counts=None):
 MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS = 4, 2
 
 
+# What `mask_counts`, `confusion_counts` and `boundary_counts` check alike, in the order they check it: _count_front, the class count
+# (_count_classes), then _count_layers; a wrapper's own checks go between them.
+def _count_front(op, scores, label_maps, gt, *outs):
+    """The layer lists and the ground truth: (scores, label_maps, B, H, W)."""
+    scores, label_maps = list(scores or ()), list(label_maps or ())
+    L.require_gpu(gt, *outs, *scores, *label_maps)
+    if not scores and not label_maps or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
+        raise L.DasacError("{} takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
+            op, MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
+    if gt.dtype != torch.int64 or gt.dim() != 3:
+        raise L.DasacError("{}: gt must be int64 [B,H,W] (got {} {})".format(op, gt.dtype, tuple(gt.shape)))
+    return (scores, label_maps) + tuple(gt.shape)
+
+
+def _count_classes(op, scores, given, out_name):
+    """The class count: from the first score tensor, else what `given()` reads from the output tensor or `num_classes`."""
+    Cn = scores[0].shape[1] if scores else given()
+    if Cn is None:
+        raise L.DasacError("{}: label maps alone do not tell the class count; pass {} or num_classes".format(op, out_name))
+    return Cn
+
+
+def _count_layers(op, scores, label_maps, gt, B, Cn, H, W, map_dtypes):
+    """Every layer's dtype and shape: contiguous (scores, label_maps, gt), the padded pointer slots and the uint8-map mask."""
+    for s in scores:
+        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
+            raise L.DasacError("{}: a score tensor must be float32 {} (got {} {})".format(op, (B, Cn, H, W), s.dtype, tuple(s.shape)))
+    kinds = " or ".join(str(d).replace("torch.", "") for d in map_dtypes)
+    for m in label_maps:
+        if m.dtype not in map_dtypes or tuple(m.shape) != (B, H, W):
+            raise L.DasacError("{}: a label map must be {} {} (got {} {})".format(op, kinds, (B, H, W), m.dtype, tuple(m.shape)))
+    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
+    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
+    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
+    return scores, label_maps, gt, sp, mp, sum(1 << i for i, m in enumerate(label_maps) if m.dtype == torch.uint8)
+
+
 def mask_counts(scores, label_maps, gt, counts=None, ignore_index=255, num_classes=None):
     """Validation counts of several mask layers against one ground truth in ONE launch (train.py:386-399, utils/metrics.py:18-39).
     scores: up to 4 fp32 [B,C,H,W] tensors (arg-max, first maximum wins); label_maps: up to 2 int64 [B,H,W] maps (255 = no label);
     gt int64 [B,H,W].  Accumulates (tp, fp, fn) per layer into `counts` (int64 [L,3,C], scores first, then label maps; allocated
     zeroed when None) and returns it.  With label maps only, C comes from `counts` or `num_classes`."""
     lib = L.load()
-    scores, label_maps = list(scores or ()), list(label_maps or ())
-    L.require_gpu(gt, counts, *scores, *label_maps)
+    scores, label_maps, B, H, W = _count_front("mask_counts", scores, label_maps, gt, counts)
+    Cn = _count_classes("mask_counts", scores, lambda: counts.shape[2] if counts is not None else num_classes, "counts")
+    scores, label_maps, gt, sp, mp, _ = _count_layers("mask_counts", scores, label_maps, gt, B, Cn, H, W, (torch.int64,))
     n_layers = len(scores) + len(label_maps)
-    if n_layers == 0 or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
-        raise L.DasacError("mask_counts takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
-            MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
-    if gt.dtype != torch.int64 or gt.dim() != 3:
-        raise L.DasacError("mask_counts: gt must be int64 [B,H,W] (got {} {})".format(gt.dtype, tuple(gt.shape)))
-    B, H, W = gt.shape
-    Cn = scores[0].shape[1] if scores else (counts.shape[2] if counts is not None else num_classes)
-    if Cn is None:
-        raise L.DasacError("mask_counts: label maps alone do not tell the class count; pass counts or num_classes")
-    for s in scores:
-        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
-            raise L.DasacError("mask_counts: a score tensor must be float32 {} (got {} {})".format((B, Cn, H, W), s.dtype, tuple(s.shape)))
-    for m in label_maps:
-        if m.dtype != torch.int64 or tuple(m.shape) != (B, H, W):
-            raise L.DasacError("mask_counts: a label map must be int64 {} (got {} {})".format((B, H, W), m.dtype, tuple(m.shape)))
     if counts is None:
         counts = torch.zeros((n_layers, 3, Cn), dtype=torch.int64, device=gt.device)
     elif counts.dtype != torch.int64 or tuple(counts.shape) != (n_layers, 3, Cn) or not counts.is_contiguous():
         raise L.DasacError("mask_counts accumulates into a contiguous int64 [{},3,{}] tensor (got {} {})".format(
             n_layers, Cn, counts.dtype, tuple(counts.shape)))
-    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
-    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
-    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
     L.check(lib.dasac_mask_counts(*sp, *mp, gt.data_ptr(), B, Cn, H * W, int(ignore_index), counts.data_ptr(), L.stream_ptr()),
             "dasac_mask_counts")
     return counts
@@ -1275,24 +1295,11 @@ def confusion_counts(scores, label_maps, gt, confusion=None, reliability=None, b
     hit); `logits_layers` lists the indices into `scores` that hold logits -- their confidence is the soft-max maximum -- the others
     hold probabilities.  With label maps only, C comes from `confusion` or `num_classes`.  Returns (confusion, reliability or None)."""
     lib = L.load()
-    scores, label_maps = list(scores or ()), list(label_maps or ())
-    L.require_gpu(gt, confusion, reliability, *scores, *label_maps)
+    op = "confusion_counts"
+    scores, label_maps, B, H, W = _count_front(op, scores, label_maps, gt, confusion, reliability)
+    Cn = _count_classes(op, scores, lambda: confusion.shape[1] - 1 if confusion is not None else num_classes, "confusion")
+    scores, label_maps, gt, sp, mp, u8_mask = _count_layers(op, scores, label_maps, gt, B, Cn, H, W, (torch.int64, torch.uint8))
     n_layers = len(scores) + len(label_maps)
-    if n_layers == 0 or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
-        raise L.DasacError("confusion_counts takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
-            MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
-    if gt.dtype != torch.int64 or gt.dim() != 3:
-        raise L.DasacError("confusion_counts: gt must be int64 [B,H,W] (got {} {})".format(gt.dtype, tuple(gt.shape)))
-    B, H, W = gt.shape
-    Cn = scores[0].shape[1] if scores else (confusion.shape[1] - 1 if confusion is not None else num_classes)
-    if Cn is None:
-        raise L.DasacError("confusion_counts: label maps alone do not tell the class count; pass confusion or num_classes")
-    for s in scores:
-        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
-            raise L.DasacError("confusion_counts: a score tensor must be float32 {} (got {} {})".format((B, Cn, H, W), s.dtype, tuple(s.shape)))
-    for m in label_maps:
-        if m.dtype not in (torch.int64, torch.uint8) or tuple(m.shape) != (B, H, W):
-            raise L.DasacError("confusion_counts: a label map must be int64 or uint8 {} (got {} {})".format((B, H, W), m.dtype, tuple(m.shape)))
     if confusion is None:
         confusion = torch.zeros((n_layers, Cn + 1, Cn + 1), dtype=torch.int64, device=gt.device)
     elif confusion.dtype != torch.int64 or tuple(confusion.shape) != (n_layers, Cn + 1, Cn + 1) or not confusion.is_contiguous():
@@ -1313,10 +1320,6 @@ def confusion_counts(scores, label_maps, gt, confusion=None, reliability=None, b
         elif reliability.dtype != torch.int64 or tuple(reliability.shape) != (len(scores), Cn, bins, 2) or not reliability.is_contiguous():
             raise L.DasacError("confusion_counts accumulates into a contiguous int64 [{},{},bins,2] reliability tensor (got {} {})".format(
                 len(scores), Cn, reliability.dtype, tuple(reliability.shape)))
-    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
-    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
-    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
-    u8_mask = sum(1 << i for i, m in enumerate(label_maps) if m.dtype == torch.uint8)
     L.check(lib.dasac_confusion_counts(*sp, *mp, u8_mask, gt.data_ptr(), B, Cn, H * W, int(ignore_index), confusion.data_ptr(),
                                        L.ptr(reliability), bins, sum(1 << i for i in logits_layers), L.stream_ptr()),
             "dasac_confusion_counts")
@@ -1336,38 +1339,21 @@ def boundary_counts(scores, label_maps, gt, table=None, radius=8, ignore_index=2
     in the ground truth, pred by its slot in the predicted map, both (prediction == ground truth) by the larger of the two.  With
     label maps only, C comes from `table` or `num_classes`.  driver.summarise_boundary reads the tables."""
     lib = L.load()
-    scores, label_maps = list(scores or ()), list(label_maps or ())
-    L.require_gpu(gt, table, *scores, *label_maps)
-    n_layers = len(scores) + len(label_maps)
-    if n_layers == 0 or len(scores) > MASK_COUNTS_MAX_SCORES or len(label_maps) > MASK_COUNTS_MAX_MAPS:
-        raise L.DasacError("boundary_counts takes 1..{} score tensors and / or 1..{} label maps (got {} and {})".format(
-            MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS, len(scores), len(label_maps)))
-    if gt.dtype != torch.int64 or gt.dim() != 3:
-        raise L.DasacError("boundary_counts: gt must be int64 [B,H,W] (got {} {})".format(gt.dtype, tuple(gt.shape)))
-    B, H, W = gt.shape
+    op = "boundary_counts"
+    scores, label_maps, B, H, W = _count_front(op, scores, label_maps, gt, table)
     if table is not None and (table.dtype != torch.int64 or table.dim() != 4):
         raise L.DasacError("boundary_counts accumulates into an int64 [L,radius+1,5,C] tensor (got {} {})".format(table.dtype, tuple(table.shape)))
-    Cn = scores[0].shape[1] if scores else (table.shape[3] if table is not None else num_classes)
-    if Cn is None:
-        raise L.DasacError("boundary_counts: label maps alone do not tell the class count; pass table or num_classes")
+    Cn = _count_classes(op, scores, lambda: table.shape[3] if table is not None else num_classes, "table")
     radius = int(table.shape[1]) - 1 if table is not None else int(radius)
     if not 1 <= radius <= BOUNDARY_MAX_RADIUS:
         raise L.DasacError("boundary_counts: the radius must be in 1..{} (got {})".format(BOUNDARY_MAX_RADIUS, radius))
-    for s in scores:
-        if s.dtype != torch.float32 or tuple(s.shape) != (B, Cn, H, W):
-            raise L.DasacError("boundary_counts: a score tensor must be float32 {} (got {} {})".format((B, Cn, H, W), s.dtype, tuple(s.shape)))
-    for m in label_maps:
-        if m.dtype not in (torch.int64, torch.uint8) or tuple(m.shape) != (B, H, W):
-            raise L.DasacError("boundary_counts: a label map must be int64 or uint8 {} (got {} {})".format((B, H, W), m.dtype, tuple(m.shape)))
+    scores, label_maps, gt, sp, mp, u8_mask = _count_layers(op, scores, label_maps, gt, B, Cn, H, W, (torch.int64, torch.uint8))
+    n_layers = len(scores) + len(label_maps)
     shape = (n_layers, radius + 1, len(BOUNDARY_ROWS), Cn)
     if table is None:
         table = torch.zeros(shape, dtype=torch.int64, device=gt.device)
     elif tuple(table.shape) != shape or not table.is_contiguous():
         raise L.DasacError("boundary_counts accumulates into a contiguous int64 {} tensor (got {} {})".format(shape, table.dtype, tuple(table.shape)))
-    scores, label_maps, gt = [_c(s) for s in scores], [_c(m) for m in label_maps], _c(gt)
-    sp = [s.data_ptr() for s in scores] + [0] * (MASK_COUNTS_MAX_SCORES - len(scores))
-    mp = [m.data_ptr() for m in label_maps] + [0] * (MASK_COUNTS_MAX_MAPS - len(label_maps))
-    u8_mask = sum(1 << i for i, m in enumerate(label_maps) if m.dtype == torch.uint8)
     need = lib.dasac_boundary_counts_workspace(n_layers, B, H, W)
     ws = L.workspace(need, gt.device)
     L.check(lib.dasac_boundary_counts(*sp, *mp, u8_mask, gt.data_ptr(), B, Cn, H, W, radius, int(ignore_index), table.data_ptr(),

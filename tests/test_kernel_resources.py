@@ -41,6 +41,15 @@ def _asm(tmp_path, src):
     return out.read_text()
 
 
+def _kernel_meta(txt):
+    """{kernel name: (scratch bytes, VGPRs, static LDS bytes)} from the code object metadata of an assembly listing"""
+    meta = {}
+    for block in re.split(r"\n\s+- \.agpr_count:", txt.split("amdhsa.kernels:")[1])[1:]:
+        field = lambda key: re.search(r"\." + key + r":\s+(\S+)", block).group(1)
+        meta[field("name")] = (int(field("private_segment_fixed_size")), int(field("vgpr_count")), int(field("group_segment_fixed_size")))
+    return meta
+
+
 def _loops(lines):
     """Loops of a kernel body as lists of lines, from LLVM's own block annotations ("Loop Header: Depth=" on the header block,
     "in Loop: Header=BBx_y" on every other block of the loop): [(lines of all blocks of the loop, #MFMA)].  (Round 6: the earlier
@@ -70,12 +79,11 @@ def _loops(lines):
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_hot_gemm_loops_have_no_scratch_fit_their_occupancy_and_keep_their_instruction_diet(tmp_path):
     txt = _asm(tmp_path, "conv_igemm")
-    meta = {m.group(1): (int(m.group(2)), int(m.group(3))) for m in re.finditer(
-        r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size: (\d+)\n(?:.*\n){0,8}?\s+\.vgpr_count:\s+(\d+)", txt)}
+    meta = _kernel_meta(txt)
     for key, (vgpr_budget, scratch_budget, diet) in HOT.items():
         names = [n for n in meta if key in n]
         assert len(names) == 1, (key, names)
-        scratch, vgprs = meta[names[0]]
+        scratch, vgprs, _ = meta[names[0]]
         assert vgprs <= vgpr_budget, (key, vgprs)
         assert scratch <= scratch_budget, (key, scratch)
         body = txt[txt.index("\n" + names[0] + ":"):]
@@ -110,12 +118,11 @@ POOL = {"maxpool_bwd_3s2p1": (64, 0, 200)}                    # 2 x 4 pixels per
 @pytest.mark.parametrize("src,table", [("head", HEAD), ("pointwise", POOL)])
 def test_streaming_head_kernels_keep_their_registers_and_instruction_counts(tmp_path, src, table):
     txt = _asm(tmp_path, src)
-    meta = {m.group(1): (int(m.group(2)), int(m.group(3))) for m in re.finditer(
-        r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size: (\d+)\n(?:.*\n){0,8}?\s+\.vgpr_count:\s+(\d+)", txt)}
+    meta = _kernel_meta(txt)
     for key, (vgpr_budget, scratch_budget, valu_budget) in table.items():
         names = [n for n in meta if key in n]
         assert len(names) == 1, (key, names)
-        scratch, vgprs = meta[names[0]]
+        scratch, vgprs, _ = meta[names[0]]
         assert vgprs <= vgpr_budget and scratch <= scratch_budget, (key, vgprs, scratch)
         body = txt[txt.index("\n" + names[0] + ":"):]
         body = body[:body.index("s_endpgm")].split("\n")

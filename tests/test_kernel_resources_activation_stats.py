@@ -2,23 +2,21 @@
 scratch at all and at most 64 VGPRs (full occupancy, 8 waves per SIMD).  Reads the code object metadata only.  Cross-compiles to
 gfx950 assembly; no GPU."""
 import os
-import re
 import shutil
 
 import pytest
 
-from test_kernel_resources import HIPCC, _asm
+from test_kernel_resources import HIPCC, _asm, _kernel_meta
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_activation_stats_kernels_use_no_scratch_and_fit_full_occupancy(tmp_path):
     txt = _asm(tmp_path, "activations")
-    meta = {m.group(1): (int(m.group(2)), int(m.group(3))) for m in re.finditer(
-        r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size: (\d+)\n(?:.*\n){0,8}?\s+\.vgpr_count:\s+(\d+)", txt)}
+    meta = _kernel_meta(txt)
     for kernel in ("activation_stats_planes", "activation_stats_finish"):
         names = [n for n in meta if kernel in n]
         assert len(names) == 1, names
-        scratch, vgprs = meta[names[0]]
+        scratch, vgprs, _ = meta[names[0]]
         print("{}: {} VGPRs, {} B scratch".format(kernel, vgprs, scratch))
         assert scratch == 0, scratch
         assert vgprs <= 64, vgprs

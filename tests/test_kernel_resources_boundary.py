@@ -3,21 +3,17 @@
 static segment from the code object, and the dynamic size the launch asks for at the largest R and C, restated from the file's own
 layout.  Reads the code object metadata only.  Cross-compiles to gfx950 assembly; no GPU."""
 import os
-import re
 import shutil
 
 import pytest
 
-from test_kernel_resources import HIPCC, _asm
+from test_kernel_resources import HIPCC, _asm, _kernel_meta
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_boundary_kernels_use_no_scratch_128_vgprs_and_64_kb_of_lds(tmp_path):
     txt = _asm(tmp_path, "boundary")
-    meta = {}
-    for block in re.split(r"\n\s+- \.agpr_count:", txt.split("amdhsa.kernels:")[1])[1:]:
-        field = lambda key: re.search(r"\." + key + r":\s+(\S+)", block).group(1)
-        meta[field("name")] = (int(field("private_segment_fixed_size")), int(field("vgpr_count")), int(field("group_segment_fixed_size")))
+    meta = _kernel_meta(txt)
     names = sorted(meta)
     assert len(names) == 3 and sum("boundary_prepare" in n for n in names) == 2 and sum("boundary_stencil" in n for n in names) == 1, names
     for name in names:

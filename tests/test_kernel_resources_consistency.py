@@ -2,24 +2,22 @@
 scratch at all and at most 128 VGPRs -- the budget csrc/validation.hip states for its counting kernels, four waves per SIMD.  Reads
 the code object metadata only.  Cross-compiles to gfx950 assembly; no GPU."""
 import os
-import re
 import shutil
 
 import pytest
 
-from test_kernel_resources import HIPCC, _asm
+from test_kernel_resources import HIPCC, _asm, _kernel_meta
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_view_consistency_kernels_use_no_scratch_and_keep_four_waves_per_simd(tmp_path):
     txt = _asm(tmp_path, "consistency")
-    meta = {m.group(1): (int(m.group(2)), int(m.group(3))) for m in re.finditer(
-        r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size: (\d+)\n(?:.*\n){0,8}?\s+\.vgpr_count:\s+(\d+)", txt)}
+    meta = _kernel_meta(txt)
     names = [n for n in meta if "view_consistency" in n]
     assert len(names) == 3, names                          # C = 19 with T = 2 and T = 4 compiled in, and the runtime path
     assert sorted(meta) == sorted(names), sorted(meta)     # every kernel of the file
     for name in names:
-        scratch, vgprs = meta[name]
+        scratch, vgprs, _ = meta[name]
         print("{}: {} VGPRs, {} B scratch".format(name, vgprs, scratch))
         assert scratch == 0, (name, scratch)
         assert vgprs <= 128, (name, vgprs)

@@ -2,12 +2,11 @@
 siblings in test_kernel_resources.py: at most 168 VGPRs (3 waves per SIMD), at most 64 bytes of scratch, and no scratch
 instruction or SGPR spill (v_readlane / v_writelane) inside a loop that carries MFMAs.  Cross-compiles to gfx950 assembly; no GPU."""
 import os
-import re
 import shutil
 
 import pytest
 
-from test_kernel_resources import HIPCC, _asm, _loops
+from test_kernel_resources import HIPCC, _asm, _kernel_meta, _loops
 
 KERNEL = "conv_wgrad_batched"
 
@@ -15,11 +14,10 @@ KERNEL = "conv_wgrad_batched"
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_batched_weight_gradient_kernel_fits_its_occupancy_and_keeps_its_mfma_loop_free_of_spills(tmp_path):
     txt = _asm(tmp_path, "conv_igemm")
-    meta = {m.group(1): (int(m.group(2)), int(m.group(3))) for m in re.finditer(
-        r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size: (\d+)\n(?:.*\n){0,8}?\s+\.vgpr_count:\s+(\d+)", txt)}
+    meta = _kernel_meta(txt)
     names = [n for n in meta if KERNEL in n]
     assert len(names) == 1, names
-    scratch, vgprs = meta[names[0]]
+    scratch, vgprs, _ = meta[names[0]]
     print("{}: {} VGPRs, {} B scratch".format(KERNEL, vgprs, scratch))
     assert vgprs <= 168, vgprs
     assert scratch <= 64, scratch
