@@ -33,26 +33,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import rel_err
+from fp64_yardstick import _ratio, _report
 
 pytestmark = pytest.mark.gpu
-FLOOR = 1e-6
 GSCALE = 0.37
 EPS = 1e-5           # sac.py:189 entropy epsilon
 MARGIN = 1e-4        # half-width of the excluded band around a discontinuity
 MAX_EXCLUDED = 5e-3
-
-
-def _ratio(got, ref64, aten32, extra_abs=0.0):
-    """err_hip / bound with bound = 2 * err_aten + FLOOR (+ extra_abs relative to the reference's max)."""
-    scale = float(ref64.abs().max().clamp_min(1e-30))
-    return rel_err(got, ref64) / (2.0 * rel_err(aten32, ref64) + FLOOR + extra_abs / scale)
-
-
-def _report(what, case, ratios):
-    print("{} {}: {}".format(what, case, ", ".join("{} {:.3g}".format(k, v) for k, v in ratios.items())))
-    for k, v in ratios.items():
-        assert v <= 1.0, (what, case, k, v)        # also false for NaN
 
 
 # ---- cross entropy ---------------------------------------------------------------------------------------------------------
