@@ -928,15 +928,16 @@ extern "C" int dasac_ema_chunk_elems(void) { return kEmaChunk; }
 // pairs: device array of {fast*, slow*, int64 n} (24 bytes each); chunks: device array of int32 pairs
 // (tensor id, chunk index within the tensor), SORTED by tensor id; sq: device [n_tensors + n_chunks] doubles (scratch: per-tensor
 // sums, then one partial per chunk -- summed in a fixed order, so teacher_diff is bit-identical from run to run); out: device [1].
-extern "C" int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks, float momentum,
+extern "C" int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks, double momentum,
                                 int update, double* sq, float* out, dasac_stream_t stream) {
   DASAC_REQUIRE(pairs && chunks && sq && out && n_tensors > 0 && n_chunks > 0, "ema_update: bad arguments");
   hipStream_t s = as_stream(stream);
   double* sq_chunk = sq + n_tensors;
-  // sac.py:95 multiplies by the python double (1. - momentum) cast to fp32
-  const float one_minus = (float)(1.0 - (double)momentum);
+  // sac.py:95 multiplies by the python double (1. - momentum) cast to fp32: the difference is taken from the DOUBLE momentum
+  // (1 - fl32(0.99) is 0.0099999905, fl32(1 - 0.99) is 0.01), so the momentum arrives as a double and both factors round once
+  const float one_minus = (float)(1.0 - momentum);
   hipLaunchKernelGGL(ema_chunks, dim3(n_chunks), dim3(256), 0, s, reinterpret_cast<const TensorPair*>(pairs),
-                     reinterpret_cast<const int2*>(chunks), momentum, one_minus, update, sq_chunk);
+                     reinterpret_cast<const int2*>(chunks), (float)momentum, one_minus, update, sq_chunk);
   DASAC_CHECK_LAUNCH("ema_chunks");
   hipLaunchKernelGGL(ema_tensor_sums, dim3(n_tensors), dim3(64), 0, s, reinterpret_cast<const int2*>(chunks), n_chunks, sq_chunk, sq);
   DASAC_CHECK_LAUNCH("ema_tensor_sums");

@@ -54,7 +54,7 @@ PROTOTYPES = {
     "dasac_maxpool_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "dasac_maxpool_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dasac_ema_chunk_elems": (_i, []),
-    "dasac_ema_update": (_i, [_p, _i, _p, _i, _f, _i, _p, _p, _p]),
+    "dasac_ema_update": (_i, [_p, _i, _p, _i, C.c_double, _i, _p, _p, _p]),
     "dasac_sgd_step": (_i, [_p, _i, _p, _i, _p, _p, _i, _f, _i, _p]),
     "dasac_sgd_nesterov_step": (_i, [_p, _i, _p, _i, _p, _p, _i, _f, _i, _p]),
     "dasac_adam_step": (_i, [_p, _i, _p, _i, _p, _i, C.c_double, C.c_double, C.c_double, _p]),

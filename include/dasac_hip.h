@@ -359,15 +359,20 @@ int dasac_class_state(float* running_conf, const double* class_sums, int B, int6
  * Around the convolutions.
  * dasac_bn_fold          frozen BatchNorm (models/__init__.py:29, basenet.py:97-100) as per-channel
  *     scale/shift for the conv epilogue: scale = gamma/sqrt(var+eps), shift = beta-(mean-b)*scale.
+ *     `conv_bias` (b, NULL = no bias) and `invstd` (NULL = not wanted) are optional; every other pointer is required.
  * dasac_bn_param_grads   gamma/beta (and conv-bias) gradients of the folded form from
  *     sum_rows dot[row][c] = sum dz*conv(x) (the `dot_rows` partial rows of dasac_conv_wgrad_finish) and sum_dz[c]
- *     (dasac_channel_sums or the wgrad kernel).
+ *     (dasac_channel_sums or the wgrad kernel): dgamma = invstd*(dot + (b - mean)*sum_dz), dbeta = sum_dz,
+ *     dbias = scale*sum_dz.  Each of dgamma / dbeta / dbias may be NULL and is then not written; `dot`, `mean` and `invstd`
+ *     are read only for dgamma (dgamma without them is DASAC_EINVAL); `scale` NULL = 1, `conv_bias` NULL = 0.
  * dasac_maxpool_fwd/bwd  nn.MaxPool2d (deeplabv2.py:126 ceil_mode 3x3/2; VGG 2x2/2); caller passes
  *     the resolved OH/OW.  bwd with relu_mask folds the ReLU backward of the producer.  `argmax` is an opaque byte per
  *     output handed from fwd to bwd: bits 0-6 the winning position kh*k + kw, bit 7 (windows up to 11x11) = pooled value > 0,
  *     so that the ReLU-folding backward does not read the pooled tensor (`y` is then unused; larger windows do read it).
  * dasac_ema_update       momentum teacher (sac.py:83-102) over all tensors in one launch:
- *     out[0] = sum_t ||slow_t - fast_t||_2 (before the update); slow = slow*m + fast*(1-m).
+ *     out[0] = sum_t ||slow_t - fast_t||_2 (before the update); slow = slow*m + fast*(1-m): three fp32 roundings with
+ *     the factors fl32(m) and fl32(1 - m), the difference taken in double as sac.py:95 takes it (hence `double momentum`).
+ *     update = 0 writes no slow tensor; out[0] is the same distance either way.
  *     `pairs`: device array of {const float* fast; float* slow; int64 n}; `chunks`: device (tensor, chunk) int32 pairs of
  *     dasac_ema_chunk_elems() elements, SORTED by tensor; `sq`: scratch of n_tensors + n_chunks doubles (one partial per
  *     chunk, added per tensor in a fixed order: the result is bit-identical from run to run).
@@ -484,7 +489,7 @@ size_t dasac_activation_stats_workspace(int64_t n_planes);
 int dasac_activation_stats(const void* tensors, int n_tensors, int N, int R, const int32_t* seg_bounds, int n_segments,
                            void* workspace, size_t workspace_bytes, double* table, dasac_stream_t stream);
 int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks,
-                     float momentum, int update, double* sq, float* out, dasac_stream_t stream);
+                     double momentum, int update, double* sq, float* out, dasac_stream_t stream);
 int dasac_scale_planes(const float* x, const float* plane_scale, int64_t planes, int64_t HW,
                        float* y, dasac_stream_t stream);
 int dasac_add(const float* a, const float* b, float* out, int64_t n, dasac_stream_t stream);
@@ -548,7 +553,7 @@ int dasac_bn_bwd_apply(const float* dy, const float* z, const float* mean, const
  * (taps = kh*kw of the one branch); mode / order as in dasac_conv_pack, Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K). */
 typedef struct dasac_fold_job {
   const float *gamma, *beta, *mean, *var, *conv_bias; /* conv_bias may be NULL */
-  float *scale, *shift, *invstd;
+  float *scale, *shift, *invstd;                      /* all three are written: invstd is NOT optional here */
   float eps;
   int32_t C;
 } dasac_fold_job;
@@ -568,7 +573,9 @@ int dasac_label_pad_mask(int64_t* labels, uint8_t* mask, int64_t n, int pad_labe
                          dasac_stream_t stream);
 /* nn.Dropout2d(p) in train mode (models/fcn.py:52,56): keep_scale[plane] = Bernoulli(1-p) / (1-p) for the (n, c) planes,
  * consumed by dasac_scale_planes.  Counter-based Philox4x32-10: the draw is a pure function of (seed, offset, plane) --
- * the caller advances `offset` per call; it is NOT ATen's stream (parity tests inject the mask instead). */
+ * the caller advances `offset` per call; it is NOT ATen's stream (parity tests inject the mask instead).  Plane i draws
+ * with counter = (i low word, i high word, offset low word, offset high word) and key = (seed low word, seed high word);
+ * u = (first output word >> 8) / 2^24 and the plane is kept iff u >= p.  Requires 0 <= p < 1 and planes > 0. */
 int dasac_dropout_planes(uint64_t seed, uint64_t offset, float p, int64_t planes, float* keep_scale,
                          dasac_stream_t stream);
 
