@@ -2073,7 +2073,9 @@ static int conv_wgrad_impl(bool x3, const float* dz, const float* x, const int32
   const int bm = pick_bm(Mpad);
   const int bnk = (M % 8 == 0 && bm != 32) ? wgrad_bn(Cx) : 128;
   const int splits = wgrad_splits(Mpad, Kpad, g.Npix, bm, bnk);
-  if (ws_bytes < (size_t)splits * Mpad * (Kpad + 1) * sizeof(float)) return fail(DASAC_EWORKSPACE, "conv_wgrad: workspace too small");
+  // the size function itself (the larger of both k-tile widths' split counts, so never less than this launch writes): what it
+  // states is what is asked for, whatever Cx turns out to be
+  if (ws_bytes < dasac_conv_wgrad_workspace(Nb, OH, OW, M, K)) return fail(DASAC_EWORKSPACE, "conv_wgrad: workspace too small");
   int per = (g.Npix + splits - 1) / splits;
   per = (per + kWgPix - 1) / kWgPix * kWgPix;
   const int4* tab = reinterpret_cast<const int4*>(table);

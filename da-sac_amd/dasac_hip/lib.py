@@ -226,11 +226,15 @@ _ws_cache = {}
 def workspace(nbytes, device, owner=None):
     """Per-(device, stream) grow-only scratch buffer (the C ABI never allocates).  `owner` names a buffer that belongs to
     ONE kernel family and is zero-filled when (re)allocated -- the stream-K hand-off flags of dasac_conv_gemm are
-    self-cleaning and must not be scribbled over by other ops' scratch data (include/dasac_hip.h)."""
+    self-cleaning and must not be scribbled over by other ops' scratch data (include/dasac_hip.h).
+    Returns a view of exactly `nbytes` bytes of the cached buffer (which never shrinks and starts at 1 MiB): `ws.numel()` is what
+    the caller asked for, whatever ran on the stream before, so a launcher that picks a path by its `ws_bytes` picks it by its
+    arguments alone."""
+    nbytes = int(nbytes)
     key = (device.index, torch.cuda.current_stream(device).cuda_stream, owner)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         alloc = torch.zeros if owner is not None else torch.empty
-        buf = alloc(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        buf = alloc(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
-    return buf
+    return buf[:nbytes]

@@ -99,7 +99,8 @@ int dasac_pseudo_labels(const float* probs, const uint8_t* ignore, const float* 
  *                    The workspace must be ZERO-FILLED by the caller when it is allocated and belong to one
  *                    stream at a time: its hand-off flags are self-cleaning (every launch leaves them
  *                    zero), which saves a memset per launch.
- * dasac_conv_wgrad   partial weight gradients (split over pixels) into `workspace`;
+ * dasac_conv_wgrad   partial weight gradients (split over pixels) into `workspace` of dasac_conv_wgrad_workspace bytes
+ *                    (an upper bound over both k-tile widths, checked as it stands: anything less is DASAC_EWORKSPACE);
  * dasac_conv_wgrad_finish  sums the splits, writes dW[co,ci,kh,kw] = scale[co]*G and, when `dot`
  *                    is given (single-branch convolutions only), the frozen-BN gamma gradient term sum_k W*G as
  *                    dasac_conv_wgrad_dot_rows(Cin, taps) PARTIAL rows dot[row][co] (row = a block of 64 input
