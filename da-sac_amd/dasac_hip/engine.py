@@ -461,6 +461,7 @@ class Engine:
         self._tables, self._packs, self._folds = {}, {}, {}
         self._refresh, self._fold_bufs = {}, {}
         self.probe, self._layouts = None, {}      # activation tables: off unless a probe is attached (Engine.forward)
+        self.tap = None                           # (op index, sink): hands ONE activation of a forward to the sink (Engine.forward)
         # A ReLU conv's pattern is recorded as bits when the backward pass will apply it in a stride-1 data-gradient epilogue:
         # the mask is applied by the consumer that finishes LAST in backward order = the slot's FIRST consumer in plan order.
         self._bits_wanted = [False] * plan.n_slots
@@ -640,15 +641,23 @@ class Engine:
         the last op on the launch stream.  `probe.append((table, layout, N, bounds))` receives the device table (fp64
         [n_segments, R, 6], ops.ACTIVATION_STATS_COLUMNS), the layout (`activation_layout`), the batch size and the segment
         bounds (`probe.bounds`: None, cut points, or a callable N -> bounds).  Nothing synchronises; `saved` is what it is
-        without a probe."""
+        without a probe.
+
+        With a `tap` = (op index, sink) attached (None by default) `sink(tensor)` is called right after that op has produced its
+        output (op index -1: with the input, before the first op; `tap_index` resolves a name).  No other activation is kept and
+        `saved` is what it is without the tap."""
         L.require_gpu(x)
         self.refresh(x.device, transposed=keep)
         acts = {0: x}
         saved = {"acts": acts, "aux": {}, "bits": {}}
-        probe = self.probe
+        probe, tap = self.probe, self.tap
         held = None if probe is None else [x]
+        if tap is not None and tap[0] == -1:
+            tap[1](x)
         for i, op in enumerate(self.plan.ops):
             acts[op.dst] = op.forward(self, i, saved, keep)
+            if tap is not None and tap[0] == i:
+                tap[1](acts[op.dst])
             if held is not None:
                 held.append(acts[op.dst])
             if not keep:
@@ -691,6 +700,26 @@ class Engine:
                                 relu=bool(op is not None and op.relu), row0=row0))
             row0 += int(c)
         return entries
+
+    def tap_index(self, name=None, names=None):
+        """(op index for `tap`, the tensor's name).  `name`: one of the names `activation_layout` gives under `names` ({conv module:
+        name}) -- "input" (index -1), a conv module's name, "pool@<slot>" ...; None: the tensor the classifier reads, i.e. the
+        input of the conv that makes the coarsest scores -- from the plan's output back through the upsampled operand of every
+        up2add (the 2048-channel layer4 output of the ResNet-101 DeepLab, fc7 of the VGG DeepLab, fc7 behind its Dropout2d op for FCN-8s).  An unknown name
+        raises ValueError and lists the names."""
+        layout = self.activation_layout([(0, 0, 0)] * (len(self.plan.ops) + 1), names)
+        if name is None:
+            slot = self.plan.output
+            while isinstance(self.producer[slot], Up2AddOp):
+                slot = self.producer[slot].src
+            if self.producer[slot] is not None:
+                slot = self.producer[slot].src
+            entry = [e for e in layout if e["slot"] == slot][-1]
+            return entry["op"], entry["name"]
+        for e in layout:
+            if e["name"] == name:
+                return e["op"], e["name"]
+        raise ValueError("no activation is called {!r}; the names are: {}".format(name, ", ".join(e["name"] for e in layout)))
 
     def _probe_pass(self, probe, held):
         N = held[0].shape[0]

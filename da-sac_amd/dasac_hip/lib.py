@@ -67,6 +67,9 @@ PROTOTYPES = {
     "dasac_tensor_stats": (_i, [_p, _i, _i, _p, _i, _p, _i, _p, _sz, _p, _p, _p, _p, _p, _p]),
     "dasac_activation_stats_workspace": (_sz, [_l]),
     "dasac_activation_stats": (_i, [_p, _i, _i, _i, _p, _i, _p, _sz, _p, _p]),
+    "dasac_label_nodes": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "dasac_class_feature_stats_workspace": (_sz, [_i, _i, _i]),
+    "dasac_class_feature_stats": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "dasac_scale_planes": (_i, [_p, _p, _l, _l, _p, _p]),
     "dasac_add": (_i, [_p, _p, _p, _l, _p]),
     "dasac_relu_mask": (_i, [_p, _p, _p, _l, _p]),

@@ -1522,6 +1522,93 @@ def activation_stats(tensors, bounds=None):
     return plan.run(tensors), plan
 
 
+# ----------------------------------------------------------------------------------------------
+# class-conditional feature tables (include/dasac_hip.h: dasac_label_nodes, dasac_class_feature_stats)
+# ----------------------------------------------------------------------------------------------
+CLASS_FEATURE_COLUMNS = ("sum", "sumsq")                    # last dimension of ClassFeatureTable.sums
+CLASS_FEATURE_MAX_CLASSES, CLASS_FEATURE_MAX_RADIUS, CLASS_FEATURE_MAX_PLANE = 32, 8, 1 << 30
+
+
+def label_nodes(labels, size, num_classes, radius=0):
+    """A label map at a feature map's resolution (include/dasac_hip.h: dasac_label_nodes).  labels: int64 or uint8 [N,H,W] (255, -1
+    and every value >= num_classes: no class); size: (h, w).  Returns uint8 [N,h,w]: the label at the pixel where
+    align_corners=True upsampling puts the node if that label is a class and the whole (2 radius + 1)^2 window around the pixel,
+    clipped to the image, holds it, else 255.  radius 0..8; one launch."""
+    lib = L.load()
+    L.require_gpu(labels)
+    if labels.dtype not in (torch.int64, torch.uint8) or labels.dim() != 3 or labels.numel() == 0:
+        raise L.DasacError("label_nodes takes a non-empty int64 or uint8 [N,H,W] label map (got {} {})".format(labels.dtype, tuple(labels.shape)))
+    h, w = int(size[0]), int(size[1])
+    Cn, radius = int(num_classes), int(radius)
+    if h < 1 or w < 1 or not 1 <= Cn <= 255 or not 0 <= radius <= CLASS_FEATURE_MAX_RADIUS:
+        raise L.DasacError("label_nodes: a size of at least 1 x 1, 1..255 classes and a radius in 0..{} (got {}x{}, C={}, radius={})".format(
+            CLASS_FEATURE_MAX_RADIUS, h, w, Cn, radius))
+    labels = _c(labels)
+    N, H, W = labels.shape
+    nodes = torch.empty((N, h, w), dtype=torch.uint8, device=labels.device)
+    L.check(lib.dasac_label_nodes(labels.data_ptr(), int(labels.dtype == torch.uint8), N, H, W, h, w, Cn, radius, nodes.data_ptr(),
+                                  L.stream_ptr()), "dasac_label_nodes")
+    return nodes
+
+
+class ClassFeatureTable:
+    """What `class_feature_stats` accumulates into: sums (device fp64 [C,Cf,2], CLASS_FEATURE_COLUMNS) and counts (device int64 [C],
+    the nodes of each class).  Both add over batches and over ranks."""
+
+    def __init__(self, sums, counts):
+        if sums.dtype != torch.float64 or sums.dim() != 3 or sums.shape[2] != len(CLASS_FEATURE_COLUMNS) or not sums.is_contiguous():
+            raise L.DasacError("a class feature table holds contiguous float64 [C,Cf,2] sums (got {} {})".format(sums.dtype, tuple(sums.shape)))
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (sums.shape[0],) or not counts.is_contiguous() or counts.device != sums.device:
+            raise L.DasacError("a class feature table holds contiguous int64 [{}] counts beside its sums (got {} {})".format(
+                sums.shape[0], counts.dtype, tuple(counts.shape)))
+        self.sums, self.counts = sums, counts
+
+    C = property(lambda self: int(self.sums.shape[0]))
+    Cf = property(lambda self: int(self.sums.shape[1]))
+
+    @classmethod
+    def zeros(cls, C, Cf, device):
+        return cls(torch.zeros((int(C), int(Cf), len(CLASS_FEATURE_COLUMNS)), dtype=torch.float64, device=device),
+                   torch.zeros(int(C), dtype=torch.int64, device=device))
+
+    def cpu(self):
+        return ClassFeatureTable(self.sums.cpu(), self.counts.cpu())
+
+    def __repr__(self):
+        return "ClassFeatureTable(C={}, Cf={}, device={})".format(self.C, self.Cf, self.sums.device)
+
+
+def class_feature_stats(x, nodes, num_classes, table=None):
+    """Per class and channel, the sum and the sum of squares (fp64, exact widening) of x over the positions whose node holds that
+    class, and the number of such nodes (include/dasac_hip.h: dasac_class_feature_stats).  x: fp32 [N,Cf,...]; nodes: uint8 [N,...]
+    with as many positions per sample (`label_nodes`; a value >= num_classes is no class); num_classes 1..32.  Accumulates into
+    `table` (a ClassFeatureTable; allocated zeroed when None) and returns it.  Two launches, no synchronisation, deterministic."""
+    lib = L.load()
+    if table is not None and not isinstance(table, ClassFeatureTable):
+        raise L.DasacError("class_feature_stats accumulates into a ClassFeatureTable (got {})".format(type(table).__name__))
+    L.require_gpu(x, nodes, None if table is None else table.sums, None if table is None else table.counts)
+    Cn = int(num_classes)
+    if x.dtype != torch.float32 or x.dim() < 2 or x.numel() == 0:
+        raise L.DasacError("class_feature_stats takes a non-empty float32 [N,Cf,...] tensor (got {} {})".format(x.dtype, tuple(x.shape)))
+    N, Cf = int(x.shape[0]), int(x.shape[1])
+    HW = x.numel() // (N * Cf)
+    if nodes.dtype != torch.uint8 or nodes.dim() < 1 or nodes.shape[0] != N or nodes.numel() != N * HW:
+        raise L.DasacError("class_feature_stats: nodes must be uint8 [{}, {} positions] (got {} {})".format(N, HW, nodes.dtype, tuple(nodes.shape)))
+    if not 1 <= Cn <= CLASS_FEATURE_MAX_CLASSES or not 1 <= HW < CLASS_FEATURE_MAX_PLANE or N > 65535:
+        raise L.DasacError("class_feature_stats: 1..{} classes, 1 <= H*W < 2^30, N <= 65535 (got C={}, H*W={}, N={})".format(
+            CLASS_FEATURE_MAX_CLASSES, Cn, HW, N))
+    if table is None:
+        table = ClassFeatureTable.zeros(Cn, Cf, x.device)
+    elif (table.C, table.Cf) != (Cn, Cf) or table.sums.device != x.device:
+        raise L.DasacError("class_feature_stats: a table of C={}, Cf={} on {} is needed (got {!r})".format(Cn, Cf, x.device, table))
+    x, nodes = _c(x), _c(nodes)
+    ws = L.workspace(lib.dasac_class_feature_stats_workspace(N, Cf, Cn), x.device)
+    with PROFILE.span("class_feature_stats", 0.0, None, x.numel() * 4.0):
+        L.check(lib.dasac_class_feature_stats(x.data_ptr(), nodes.data_ptr(), N, Cf, HW, Cn, table.sums.data_ptr(), table.counts.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), L.stream_ptr()), "dasac_class_feature_stats")
+    return table
+
+
 VIS_IMAGE, VIS_LABELS, VIS_SCORES, VIS_CONF = 0, 1, 2, 3
 
 

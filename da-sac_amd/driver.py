@@ -972,6 +972,15 @@ def activation_report(record, segment=0, top=10):
                 net=record.net, segment=segment, samples=(lo, hi))
 
 
+def moment_gap(mu_a, var_a, mu_b, var_b):
+    """The per-channel distance of two sets of moments that `domain_gap_report` and `class_gap_report` share (numpy float64,
+    broadcasting): num = (mu_a - mu_b)^2 + (sigma_a - sigma_b)^2, den = (var_a + var_b) / 2, 0 where num == 0, else
+    num / max(den, 1e-30)."""
+    import numpy as np
+    num = (mu_a - mu_b) ** 2 + (np.sqrt(var_a) - np.sqrt(var_b)) ** 2
+    return np.where(num == 0, 0.0, num / np.maximum(0.5 * (var_a + var_b), 1e-30))
+
+
 def domain_gap_report(a, b=None, top=10):
     """Per-layer covariate shift between two domains under the same weights: two records of the same net (segment 0 of each), or
     ONE record with two segments (segments 0 and 1: `forward_fused`'s [source; target] batch).  Copies the tables to the host.
@@ -1001,8 +1010,7 @@ def domain_gap_report(a, b=None, top=10):
         nb = float((b.bounds[sb + 1] - b.bounds[sb]) * e["H"] * e["W"])
         mu_a, mu_b = Ta[rows, 0] / na, Tb[rows, 0] / nb
         var_a, var_b = np.maximum(Ta[rows, 1] / na - mu_a ** 2, 0.0), np.maximum(Tb[rows, 1] / nb - mu_b ** 2, 0.0)
-        num = (mu_a - mu_b) ** 2 + (np.sqrt(var_a) - np.sqrt(var_b)) ** 2
-        gap_c = np.where(num == 0, 0.0, num / np.maximum(0.5 * (var_a + var_b), 1e-30))
+        gap_c = moment_gap(mu_a, var_a, mu_b, var_b)
         dead_a, dead_b = Ta[rows, 5] == na, Tb[rows, 5] == nb
         alive = ~(dead_a & dead_b)
         worst = int(np.argmax(gap_c))
@@ -1048,6 +1056,201 @@ def format_domain_gap_report(report, top=10):
               str(l["dead_only_a"]), str(l["dead_only_b"]), str(l["dead_both"])] for l in rows]
     lines = _fixed_width(head, cols, width, [l["name"] for l in rows], cells)
     lines.append("{}: {} layers; largest gap: {}".format(report["net"], len(L_), rows[0]["name"] if rows else "none"))
+    return "\n".join(lines)
+
+
+# --------------------------------------------------------------------------------------------------
+# class-conditional feature tables: per-class prototypes of one activation and the per-class domain gap (no counterpart in the
+# reference)
+# --------------------------------------------------------------------------------------------------
+class ClassFeatureRecord:
+    """What `class_features` returns: table (dasac_hip.ops.ClassFeatureTable: sums fp64 [C,Cf,2], counts int64 [C], on the device),
+    layer (the resolved name of the tapped activation), Cf, radius, labels ("given" / "prediction"), num_classes, net ("backbone" /
+    "slow_net") and batches (how many went in)."""
+
+    def __init__(self, table, layer, Cf, radius, labels, num_classes, net, batches=0):
+        self.table, self.layer, self.Cf, self.radius, self.labels = table, layer, int(Cf), int(radius), labels
+        self.num_classes, self.net, self.batches = int(num_classes), net, int(batches)
+
+    def __repr__(self):
+        return "ClassFeatureRecord(net={!r}, layer={!r}, Cf={}, C={}, radius={}, labels={!r}, batches={})".format(
+            self.net, self.layer, self.Cf, self.num_classes, self.radius, self.labels, self.batches)
+
+
+def class_features(net, batches, labels="given", layer=None, radius=2, num_classes=19, teacher=False, into=None):
+    """Per-class, per-channel moments of ONE activation of the backbone, accumulated over `batches` on the device.
+
+        src = driver.class_features(net, source_batches)                                   # ground truth
+        tgt = driver.class_features(net, target_batches, labels="prediction")              # no ground truth needed
+        print(driver.format_class_gap_report(driver.class_gap_report(src, tgt), class_names))
+
+    batches yields (image [B,3,H,W], label map [B,H,W] int64 / uint8 or None), on the device.  Per batch: one no-grad forward of
+    the student backbone (teacher=True: `slow_net`) with an engine tap on `layer` (a name of `Engine.activation_layout`; None: the
+    classifier's input, see `Engine.tap_index`), one ops.label_nodes launch that brings the label map to the activation's
+    resolution (a node keeps its class only if the whole (2 radius + 1)^2 window around its pixel holds it) and one
+    ops.class_feature_stats launch.  labels="given" takes the map as it is (ground truth, or the `teacher_labels` of a target
+    step); labels="prediction" takes the arg-max of that same forward's logits at the image's resolution (ops.infer_labels), so
+    the window speaks of predicted regions.  Eval mode, restored afterwards; teacher, class prior and optimiser are untouched.
+    The tap is detached after every forward, also when it fails.  `into`: a record to continue; a different net, layer, Cf,
+    radius, label source or class count is refused.  Tables are PER RANK: see `reduce_class_features`."""
+    from dasac_hip import engine as E
+    from dasac_hip import ops
+    if labels not in ("given", "prediction"):
+        raise ValueError("class_features: labels is \"given\" or \"prediction\" (got {!r})".format(labels))
+    core = net.module if hasattr(net, "module") else net
+    backbone, _ = _infer_backbone_and_lut(net, None, None, teacher)
+    tag = "slow_net" if (teacher and hasattr(core, "backbone")) else "backbone"
+    radius, num_classes = int(radius), int(num_classes)
+    record, eng = into, None
+    was = core.training
+    core.eval()
+    try:
+        with torch.no_grad():
+            for image, label_map in batches:
+                if backbone._engine is None or backbone._engine.stale():
+                    backbone._engine = E.Engine(backbone._plan())
+                if backbone._engine is not eng:               # once per engine: the first batch, or parameters replaced in between
+                    eng = backbone._engine
+                    index, name = eng.tap_index(layer, {m: n for n, m in backbone.named_modules()})
+                if eng.tap is not None:
+                    raise RuntimeError("class_features: the engine of {} already has a tap attached".format(tag))
+                got = []
+                eng.tap = (index, got.append)
+                try:
+                    logits = backbone._logits(image)
+                finally:
+                    eng.tap = None
+                feat = got[0]
+                if record is None:
+                    record = ClassFeatureRecord(ops.ClassFeatureTable.zeros(num_classes, feat.shape[1], feat.device), name, feat.shape[1],
+                                                radius, labels, num_classes, tag)
+                elif (record.net, record.layer, record.Cf, record.radius, record.labels, record.num_classes) != \
+                        (tag, name, int(feat.shape[1]), radius, labels, num_classes):
+                    raise ValueError("class_features: {!r} cannot take net={!r}, layer={!r}, Cf={}, radius={}, labels={!r}, C={}".format(
+                        record, tag, name, int(feat.shape[1]), radius, labels, num_classes))
+                if labels == "prediction":
+                    label_map, _ = ops.infer_labels(logits, image.shape[-2:])
+                elif label_map is None:
+                    raise ValueError("class_features: labels=\"given\" needs a label map with every batch")
+                nodes = ops.label_nodes(label_map, feat.shape[-2:], num_classes, radius)
+                ops.class_feature_stats(feat, nodes, num_classes, record.table)
+                record.batches += 1
+    finally:
+        core.train(was)
+    if record is None:
+        raise ValueError("class_features: no batches")
+    return record
+
+
+def reduce_class_features(record):
+    """Sums a record's table over the ranks of the process group, in place: one collective for `sums`, one for `counts` (both
+    add).  gloo moves device tensors with no ordering against the stream that fills them (see prep_batch), so under gloo the HOST
+    tensors are summed and the record then holds host tensors; RCCL sums on the device.  Without a process group (or with one
+    rank) nothing happens.  Returns the record."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return record
+    table = record.table.cpu() if dist.get_backend() == "gloo" else record.table
+    dist.all_reduce(table.sums)
+    dist.all_reduce(table.counts)
+    record.table = table
+    return record
+
+
+def _class_moments(record):
+    """(n [C], mu [C,Cf], var [C,Cf], dead [C,Cf]) in numpy float64 from a ClassFeatureRecord, a ClassFeatureTable or anything with
+    `sums` / `counts` (torch tensors or arrays): the one host copy."""
+    import numpy as np
+    table = getattr(record, "table", record)
+    host = lambda t, dt: t.detach().cpu().numpy().astype(dt) if isinstance(t, torch.Tensor) else np.asarray(t, dtype=dt)
+    sums, counts = host(table.sums, np.float64), host(table.counts, np.int64)
+    assert sums.ndim == 3 and sums.shape[2] == 2 and counts.shape == (sums.shape[0],), (sums.shape, counts.shape)
+    n = np.maximum(counts, 1).astype(np.float64)[:, None]
+    mu = sums[..., 0] / n
+    var = np.maximum(sums[..., 1] / n - mu ** 2, 0.0)
+    return counts, mu, var, sums[..., 1] == 0
+
+
+def _row_distance(mu_a, var_a, dead_a, mu_b, var_b, dead_b):
+    """D of two class rows: `moment_gap` averaged over the channels that are not dead (all zero) in both; 0 if there is none."""
+    alive = ~(dead_a & dead_b)
+    return float(moment_gap(mu_a, var_a, mu_b, var_b)[alive].mean()) if alive.any() else 0.0
+
+
+def class_gap_report(a, b=None, ignore_classes=(), min_nodes=16, top=5):
+    """Reads two class feature tables -- `a` (say, the source) against `b` (the target) -- or `a` alone.  Host-side float64; THE ONE
+    PLACE that copies the tables to the host.  Per class c with n_c nodes: mu_c[f] = sum / n_c, var_c[f] = max(sumsq / n_c - mu^2,
+    0).  D(row, row') is `domain_gap_report`'s per-channel formula (`moment_gap`) averaged over the channels not dead in both rows.
+    A class counts in a table when it is not in `ignore_classes` and has at least `min_nodes` nodes there.  With `b`, per class c
+    that counts in both:
+      gap[c]      D(a_c, b_c): how far the class moved between the domains;
+      nearest[c]  argmin over k != c (k counting in a) of D(b_c, a_k), with nearest_distance[c];
+      margin[c]   nearest_distance[c] / gap[c]: below 1, b's class c lies nearer to ANOTHER class of a than to its own (inf when
+                  gap is 0).
+    Returns a plain dict: gap, nearest (-1: none), nearest_distance, margin (numpy [C]; NaN for the classes in `skipped`), matrix
+    [C,C] = D(b_c, a_k) (NaN where c does not count in b or k not in a), counts_a, counts_b, skipped ({class: reason} -- "ignored",
+    "absent" or "under min_nodes"), top (the `top` classes by margin, smallest first), layer, Cf.
+    With b=None the same within `a`: matrix = D(a_c, a_k) with a zero diagonal, gap = 0, margin = inf, and top lists the classes by
+    nearest_distance, smallest first -- class separability.  Refuses tables of different shapes or, for records, layers."""
+    import numpy as np
+    within = b is None
+    if within:
+        b = a
+    na, mu_a, var_a, dead_a = _class_moments(a)
+    nb, mu_b, var_b, dead_b = _class_moments(b)
+    if mu_a.shape != mu_b.shape:
+        raise ValueError("class_gap_report: tables of different shapes {} and {}".format(mu_a.shape, mu_b.shape))
+    if getattr(a, "layer", None) != getattr(b, "layer", None):
+        raise ValueError("class_gap_report: records of different layers {!r} and {!r}".format(getattr(a, "layer", None), getattr(b, "layer", None)))
+    C, Cf = mu_a.shape
+    ignored = set(int(c) for c in ignore_classes)
+    in_a = [c not in ignored and na[c] >= max(int(min_nodes), 1) for c in range(C)]
+    in_b = [c not in ignored and nb[c] >= max(int(min_nodes), 1) for c in range(C)]
+    skipped = {}
+    for c in range(C):
+        if not (in_a[c] and in_b[c]):
+            skipped[c] = "ignored" if c in ignored else ("absent" if min(na[c], nb[c]) == 0 else "under min_nodes")
+    matrix = np.full((C, C), np.nan)
+    for c in range(C):
+        for k in range(C):
+            if in_b[c] and in_a[k]:
+                matrix[c, k] = 0.0 if (within and c == k) else _row_distance(mu_b[c], var_b[c], dead_b[c], mu_a[k], var_a[k], dead_a[k])
+    gap, dist, margin = np.full(C, np.nan), np.full(C, np.nan), np.full(C, np.nan)
+    nearest = np.full(C, -1, dtype=np.int64)
+    for c in range(C):
+        if c in skipped:
+            continue
+        gap[c] = matrix[c, c]
+        others = [k for k in range(C) if k != c and in_a[k]]
+        if others:
+            nearest[c] = min(others, key=lambda k: (matrix[c, k], k))
+            dist[c] = matrix[c, nearest[c]]
+            margin[c] = dist[c] / gap[c] if gap[c] > 0 else (np.inf if dist[c] > 0 or within else np.nan)
+    key = dist if within else margin
+    order = sorted([c for c in range(C) if c not in skipped and nearest[c] >= 0], key=lambda c: (key[c], c))
+    return dict(gap=gap, nearest=nearest, nearest_distance=dist, margin=margin, matrix=matrix, counts_a=na, counts_b=nb,
+                skipped=skipped, top=order[:top], layer=getattr(a, "layer", None), Cf=Cf, within=within)
+
+
+def format_class_gap_report(report, names=None):
+    """Fixed-width text table of a `class_gap_report`: one line per class that counts, by margin (alone: by nearest distance),
+    smallest first, then one summary line.  names: class names (default: the indices)."""
+    C = len(report["gap"])
+    name = lambda c: str(c) if c < 0 or names is None else str(names[c])
+    key = report["nearest_distance"] if report["within"] else report["margin"]
+    rows = sorted([c for c in range(C) if c not in report["skipped"]], key=lambda c: (key[c] != key[c], key[c], c))
+    head = max([len("class")] + [len(name(c)) for c in rows])
+    near = max([len("nearest")] + [len(name(int(report["nearest"][c]))) for c in rows])
+    cols, width = ["n_a", "n_b", "gap", "nearest", "distance", "margin"], [9, 9, 10, near, 10, 10]
+    lines = [" ".join(["class".ljust(head)] + [c.rjust(w) for c, w in zip(cols, width)])]
+    for c in rows:
+        k = int(report["nearest"][c])
+        cells = [str(int(report["counts_a"][c])), str(int(report["counts_b"][c])), "{:.3e}".format(report["gap"][c]),
+                 name(k) if k >= 0 else "-", "{:.3e}".format(report["nearest_distance"][c]), "{:.3e}".format(report["margin"][c])]
+        lines.append(" ".join([name(c).ljust(head)] + [v.rjust(w) for v, w in zip(cells, width)]))
+    below = [c for c in rows if report["margin"][c] < 1]
+    lines.append("{}: {} channels, {} of {} classes compared, {} skipped; margin below 1: {}".format(
+        report["layer"] or "table", report["Cf"], len(rows), C, len(report["skipped"]), ", ".join(name(c) for c in below) or "none"))
     return "\n".join(lines)
 
 

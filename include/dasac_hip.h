@@ -489,6 +489,31 @@ int dasac_tensor_stats(const void* tensors, int row_bytes, int n_tensors, const 
 size_t dasac_activation_stats_workspace(int64_t n_planes);
 int dasac_activation_stats(const void* tensors, int n_tensors, int N, int R, const int32_t* seg_bounds, int n_segments,
                            void* workspace, size_t workspace_bytes, double* table, dasac_stream_t stream);
+/* Class-conditional feature tables: the moments of an activation per CLASS and channel, the class of a position taken from a
+ * label map brought to the feature map's own resolution.
+ * dasac_label_nodes  labels [N,H,W] int64 or uint8 (labels_u8), as the count kernels take them -> nodes u8 [N,h,w].  Node (i,j)
+ *     sits where align_corners=True upsampling puts it: pixel (Y(i), X(j)), Y(i) = (2*i*(H-1) + (h-1)) / (2*(h-1)) in integers
+ *     (halves round up; 0 when h == 1), X likewise.  nodes[n,i,j] = v, the label at that pixel, if 0 <= v < C and every pixel of
+ *     the window [Y-radius, Y+radius] x [X-radius, X+radius], clipped to the image, holds v; 255 otherwise.  So 255, -1 and any
+ *     value >= C leave their own node and every node whose window touches them without a class.  radius 0..8 (0: nearest
+ *     sampling), C 1..255.  Keeps prototypes to region interiors: a stride-8 feature at a contour is a mixture.
+ * dasac_class_feature_stats  x [N,Cf,HW] fp32, nodes [N,HW] u8 (any byte address).  For every class c < C <= 32 and channel f,
+ *     over all (n,p) with nodes[n,p] == c:  sums[c][f][0] += sum x,  sums[c][f][1] += sum x^2  (each x widened to double, squared
+ *     in double),  counts[c] += their number.  sums: double [C][Cf][2], counts: int64 [C]; both ACCUMULATE -- the caller
+ *     zero-fills them once and a loader's batches add up.  A node >= C belongs to no class.  There is no finite filter: a
+ *     non-finite x makes its cell non-finite (dasac_activation_stats finds those).  One 256-thread block per (sample, group of
+ *     channels) writes one partial row [C][2] per (sample, channel) to `workspace` (dasac_class_feature_stats_workspace =
+ *     N*Cf*C*16 bytes, 8-byte aligned); one lane per (channel, class) adds the samples in ascending order and then adds the
+ *     result to sums.  No floating-point atomics, every combination in a fixed order, and an element's owner thread and a
+ *     thread's summation order depend on the element's index inside its plane, never on its address: the same values give the
+ *     same bits wherever x and nodes lie.  counts uses integer adds (exact in any order).  Bad arguments (null pointers, C
+ *     outside 1..32, N outside 1..65535, HW outside 1..2^30-1, workspace too small) return DASAC_EINVAL before any launch and
+ *     leave sums and counts untouched. */
+int dasac_label_nodes(const void* labels, int labels_u8, int N, int H, int W, int h, int w, int C, int radius,
+                      uint8_t* nodes, dasac_stream_t stream);
+size_t dasac_class_feature_stats_workspace(int N, int Cf, int C);
+int dasac_class_feature_stats(const float* x, const uint8_t* nodes, int N, int Cf, int HW, int C,
+                              double* sums, int64_t* counts, void* workspace, size_t ws_bytes, dasac_stream_t stream);
 int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks,
                      double momentum, int update, double* sq, float* out, dasac_stream_t stream);
 int dasac_scale_planes(const float* x, const float* plane_scale, int64_t planes, int64_t HW,
