@@ -173,7 +173,7 @@ class ConvOp:
                                                outs=(bp.dest(bn_idx[0]), bp.dest(bn_idx[1])) if want_bn else (None, None))
             del z
             if want_bn:
-                grads[bn_idx[0]], grads[bn_idx[1]] = dg, db
+                bp.store(bn_idx, (dg, db))
             scale, invstd, want_bn = None, None, False        # what is left of BN below is the frozen one's
         else:
             scale, _, invstd = eng.fold(self)
@@ -204,7 +204,7 @@ class ConvOp:
                                              outs=(bp.dest(bn_idx[0]) if want_bn else None, bp.dest(bn_idx[1]) if want_bn else None,
                                                    bp.dest(b_idx[0]) if want_bias else None))
             if want_bn:
-                grads[bn_idx[0]], grads[bn_idx[1]] = dg, db
+                bp.store(bn_idx, (dg, db))
             if want_bias:
                 grads[b_idx[0]] = dcb
         return dz, scale
@@ -344,6 +344,42 @@ def _ver(t):
     return (t.data_ptr(), t._version)
 
 
+_tensor_data = torch.Tensor.data          # the C-level `data` descriptor of every tensor
+
+
+class TrackedParameter(torch.nn.Parameter):
+    """The class an Engine gives the parameters of its plan (`p.__class__`: the objects, their storage and every reference to
+    them stay what they are; isinstance(p, nn.Parameter) holds; pickling and state_dict give plain tensors / Parameters).
+
+    `p.data` is an alias of p with a version counter of its own, so `p.data.mul_(...)` -- the in-place update of much older
+    PyTorch code -- moves nothing that `_ver` reads and the cached packs and folds would outlive the values they were made from.
+    Here reading or assigning `p.data` moves p's own counter: whoever asks for the alias is taken to write through it.  A reader
+    costs one rebuild of that layer's caches, nothing else.  Not seen: a write through an alias taken BEFORE the last forward and
+    kept, or through a raw pointer -- `ops.bump_versions` after those."""
+
+    @property
+    def data(self):
+        torch.autograd.graph.increment_version(self)
+        return _tensor_data.__get__(self, type(self))
+
+    @data.setter
+    def data(self, value):
+        _tensor_data.__set__(self, value)
+        torch.autograd.graph.increment_version(self)
+
+
+def _keep_multi_tensor_optimisers():
+    """torch.optim takes its multi-tensor (foreach / fused) implementations only for the tensor classes on this list (Tensor and
+    nn.Parameter), by exact type; a class that behaves like them registers itself there (as torch's own DTensor does).  Without
+    it torch.optim.Adam / SGD fall back to one launch series per parameter -- slower, and rounded differently."""
+    from torch.optim.optimizer import _foreach_supported_types as types
+    if TrackedParameter not in types:
+        types.append(TrackedParameter)
+
+
+_keep_multi_tensor_optimisers()
+
+
 def _fold_key(op):
     """What a cached fold of `op` was computed from: the frozen BN's vectors (and the conv bias), or the branch biases."""
     if op.bn is None:
@@ -373,7 +409,11 @@ class _BackwardPass:
         self.eng, self.need, self.sink = eng, need, sink
         self.acts, self.aux, self.bits = saved["acts"], saved["aux"], saved.get("bits", {})
         self.grads = [None] * len(eng.params)
-        self.g = {eng.plan.output: grad_out.contiguous()}
+        g_out, out_op = grad_out.contiguous(), eng.producer[eng.plan.output]
+        if out_op is not None and out_op.relu:
+            # nobody consumes the plan's output inside the plan: a ReLU that closes it is differentiated here
+            g_out = ops.relu_mask(g_out, self.acts[eng.plan.output])
+        self.g = {eng.plan.output: g_out}
         # the d-gamma dot terms of all frozen-BN convs are slices of ONE vector: [dot_rows, cout] partial rows per layer, every
         # element written by the weight-gradient finish and added in a fixed order by bn_param_grads (no atomics, no fill)
         self.dot_pool, self.dot_used = None, 0
@@ -441,7 +481,10 @@ class Engine:
         for op in plan.ops:
             op.pidx = list(range(len(self.params), len(self.params) + len(op.params())))
             self.params += op.params()
-        self._convs = [op for op in plan.ops if isinstance(op, ConvOp)]      # the ops that own parameters and caches
+        for p in self.params:
+            if type(p) is torch.nn.Parameter:      # (another subclass keeps its class: its `.data` writes need bump_versions)
+                p.__class__ = TrackedParameter
+        self._convs =[op for op in plan.ops if isinstance(op, ConvOp)]      # the ops that own parameters and caches
         self._owners, self._geometry = [], []
         for op in self._convs:
             op.name_index_groups()
@@ -458,6 +501,7 @@ class Engine:
                 self.last_use[s] = i
                 first_consumer.setdefault(s, op)
         self.last_use[plan.output] = len(plan.ops)
+        self._check_supported()
         self._tables, self._packs, self._folds = {}, {}, {}
         self._refresh, self._fold_bufs = {}, {}
         self.probe, self._layouts = None, {}      # activation tables: off unless a probe is attached (Engine.forward)
@@ -469,10 +513,34 @@ class Engine:
             if first_consumer[op.src] is op and op.spec.stride == 1 and op.src != 0:
                 self._bits_wanted[op.src] = True
 
+    def _check_supported(self):
+        """Refuses, before any kernel runs, the plan shapes the backward pass has no code for."""
+        plan = self.plan
+
+        def refuse(i, op, why):
+            raise ValueError("dasac_hip engine: op {} ({} {} -> slot {}) {}".format(
+                i, op.kind, "slots {}".format(op.inputs()) if len(op.inputs()) > 1 else "slot {}".format(op.src), op.dst, why))
+
+        live = {plan.output}
+        for i in range(len(plan.ops) - 1, -1, -1):
+            op = plan.ops[i]
+            if op.dst not in live:
+                refuse(i, op, "never reaches the plan's output (slot {}): the backward pass would wait for its gradient".format(plan.output))
+            live.update(op.inputs())
+        for i, op in enumerate(plan.ops):
+            if isinstance(op, PoolOp) and self.consumers[op.src] != 1:
+                refuse(i, op, "is a pool whose source has {} consumers: the pool's backward writes its source's gradient "
+                              "alone".format(self.consumers[op.src]))
+            if isinstance(op, ConvOp) and op.spec.stride != 1 and op.src != 0 and \
+                    (op.spec.taps != 1 or op.spec.branches[0][3] != 0):
+                refuse(i, op, "is a stride-{} conv with {} taps (padding {}) that does not read the input image: the strided "
+                              "data gradient exists for unpadded 1x1 convs only".format(op.spec.stride, op.spec.taps, op.spec.branches[0][3]))
+
     def stale(self):
         """True when a module no longer holds the Parameter objects (or conv geometry) this engine captured:
         `load_state_dict(assign=True)`, `m.weight = nn.Parameter(...)`, parametrizations, edited dilation/padding.
-        In-place updates (optimisers, copy_) are NOT stale -- the caches follow the version counters."""
+        In-place updates (optimisers, copy_, `p.data.mul_`: TrackedParameter) are NOT stale -- the caches follow the version
+        counters.  A write through a raw pointer, or into a BN buffer's `.data`, moves no counter: `ops.bump_versions` after it."""
         return any(getattr(m, a) is not p for (m, a), p in zip(self._owners, self.params)) or \
             any(op.geometry() != geo for op, geo in self._geometry)
 
