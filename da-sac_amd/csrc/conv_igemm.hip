@@ -1413,7 +1413,8 @@ __global__ __launch_bounds__(256) void pack_weights_multi(const dasac_pack_job* 
 // fp32 packed weights [(k/4)][Mpad][4] -> split-bf16 operands: K-step t (16 k) holds four slots of Mpad
 // 16-byte words, slot 2*o + h = octet o (k = 16t + 8o .. +7), h = 0 heads / 1 tails -- the same addressing
 // as the fp32 tile (slot == quad), so conv_gemm's weight path is shared.
-__global__ void pack_x3(const f32x4* Wp, f32x4* Wx, int Mpad, int Kpad) {   // Wx may alias Wp (in-place conversion)
+// Both operands are read and written through element-aligned vectors: a packed operand may sit at any 4-byte phase.
+__global__ void pack_x3(const f32x4u* Wp, f32x4u* Wx, int Mpad, int Kpad) {   // Wx may alias Wp (in-place conversion)
   const int64_t total = (int64_t)(Kpad / 8) * Mpad;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t oct = i / Mpad;                  // global octet index = 2*t + o
@@ -1776,6 +1777,7 @@ extern "C" int dasac_conv_table(const int32_t* kh, const int32_t* kw, const int3
                                 dasac_stream_t stream) {
   DASAC_REQUIRE(kh && kw && dil && pad && table, "conv_table: null pointer");
   DASAC_REQUIRE(n_branches >= 1 && n_branches <= 4 && C > 0, "conv_table: bad branches/C");
+  DASAC_REQUIRE(((uintptr_t)table & 15) == 0, "conv_table: misaligned table (16-byte rows)");
   TapGroups tg;
   tg.n = n_branches;
   int taps = 0;
@@ -1811,6 +1813,7 @@ extern "C" int dasac_pack_chunk_elems(void) { return kPackChunk; }
 
 extern "C" int dasac_conv_pack_multi(const dasac_pack_job* jobs, const int32_t* chunks, int n_chunks, dasac_stream_t stream) {
   DASAC_REQUIRE(jobs && chunks && n_chunks > 0, "conv_pack_multi: bad arguments");
+  DASAC_REQUIRE((((uintptr_t)jobs | (uintptr_t)chunks) & 7) == 0, "conv_pack_multi: misaligned job table / chunk list");
   hipLaunchKernelGGL(pack_weights_multi, dim3(n_chunks), dim3(256), 0, as_stream(stream), jobs, reinterpret_cast<const int2*>(chunks));
   DASAC_CHECK_LAUNCH("pack_weights_multi");
   return DASAC_OK;
@@ -1859,6 +1862,7 @@ static int conv_gemm_impl(bool x3, const float* x, const float* packed, const in
                           int pix_begin, int pix_count, int schedule, void* workspace, size_t ws_bytes, dasac_stream_t stream,
                           float* stats = nullptr) {
   DASAC_REQUIRE(x && packed && table && out, "conv_gemm: null pointer");
+  DASAC_REQUIRE(((uintptr_t)table & 15) == 0, "conv_gemm: misaligned table (16-byte rows)");
   DASAC_REQUIRE(!stats || (!x3 && !mask_bits && !relu_bits_out && dasac_conv_gemm_bits_ok(M, Cx) && ostride == 1),
                 "conv_gemm_stats: needs the 128-row fp32 tile with Cx %% 16 == 0 (dasac_conv_gemm_stats_ok), no bit masks");
   DASAC_REQUIRE(!(mask && mask_bits), "conv_gemm: give the ReLU pattern as fp32 mask OR as bit mask");
@@ -1953,6 +1957,7 @@ extern "C" int dasac_conv_gemm_batched(const float* x, const float* packed, cons
                                        dasac_stream_t stream) {
   DASAC_REQUIRE(batch >= 1 && batch <= 65535, "conv_gemm_batched: batch %d outside 1..65535 (grid y)", batch);
   DASAC_REQUIRE(x && packed && table && out, "conv_gemm_batched: null pointer");
+  DASAC_REQUIRE(((uintptr_t)table & 15) == 0, "conv_gemm_batched: misaligned table (16-byte rows)");
   DASAC_REQUIRE(Cx > 0 && Cx % kBK == 0, "conv_gemm_batched: gathered channels %d must be a multiple of %d", Cx, kBK);
   GemmGeom g;
   const int Mpad = dasac_conv_mpad(M), Kloop = (K + kBK - 1) / kBK * kBK;
@@ -2010,7 +2015,7 @@ extern "C" int dasac_conv_pack_x3(const float* packed, int M, int K, void* packe
   DASAC_REQUIRE(packed && packed_x3, "conv_pack_x3: null pointer");
   const int Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K);
   hipLaunchKernelGGL(pack_x3, dim3(stream_grid((int64_t)(Kpad / 8) * Mpad, 256)), dim3(256), 0, as_stream(stream),
-                     reinterpret_cast<const f32x4*>(packed), reinterpret_cast<f32x4*>(packed_x3), Mpad, Kpad);
+                     reinterpret_cast<const f32x4u*>(packed), reinterpret_cast<f32x4u*>(packed_x3), Mpad, Kpad);
   DASAC_CHECK_LAUNCH("pack_x3");
   return DASAC_OK;
 }
@@ -2066,6 +2071,7 @@ extern "C" size_t dasac_conv_wgrad_workspace(int Nb, int OH, int OW, int M, int 
 static int conv_wgrad_impl(bool x3, const float* dz, const float* x, const int32_t* table, int Nb, int Cx, int H, int W, int OH,
                            int OW, int stride, int M, int K, void* workspace, size_t ws_bytes, dasac_stream_t stream) {
   DASAC_REQUIRE(dz && x && table && workspace, "conv_wgrad: null pointer");
+  DASAC_REQUIRE(((uintptr_t)table & 15) == 0, "conv_wgrad: misaligned table (16-byte rows)");
   GemmGeom g;
   const int Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K);
   int rc = fill_geom(g, Nb, Cx, H, W, OH, OW, stride, M, Mpad, Kpad, OH, OW, 1);

@@ -864,6 +864,7 @@ extern "C" int dasac_bn_fold(const float* gamma, const float* beta, const float*
 
 extern "C" int dasac_bn_fold_multi(const dasac_fold_job* jobs, const int32_t* chunks, int n_chunks, dasac_stream_t stream) {
   DASAC_REQUIRE(jobs && chunks && n_chunks > 0, "bn_fold_multi: bad arguments");
+  DASAC_REQUIRE((((uintptr_t)jobs | (uintptr_t)chunks) & 7) == 0, "bn_fold_multi: misaligned job table / chunk list");
   hipLaunchKernelGGL(bn_fold_multi, dim3(n_chunks), dim3(256), 0, as_stream(stream), jobs, reinterpret_cast<const int2*>(chunks));
   DASAC_CHECK_LAUNCH("bn_fold_multi");
   return DASAC_OK;
@@ -931,6 +932,7 @@ extern "C" int dasac_ema_chunk_elems(void) { return kEmaChunk; }
 extern "C" int dasac_ema_update(const void* pairs, int n_tensors, const int32_t* chunks, int n_chunks, double momentum,
                                 int update, double* sq, float* out, dasac_stream_t stream) {
   DASAC_REQUIRE(pairs && chunks && sq && out && n_tensors > 0 && n_chunks > 0, "ema_update: bad arguments");
+  DASAC_REQUIRE((((uintptr_t)pairs | (uintptr_t)chunks | (uintptr_t)sq) & 7) == 0, "ema_update: misaligned pair table / chunk list / sq");
   hipStream_t s = as_stream(stream);
   double* sq_chunk = sq + n_tensors;
   // sac.py:95 multiplies by the python double (1. - momentum) cast to fp32: the difference is taken from the DOUBLE momentum
@@ -945,6 +947,9 @@ extern "C" int dasac_ema_update(const void* pairs, int n_tensors, const int32_t*
   DASAC_CHECK_LAUNCH("ema_finish");
   return DASAC_OK;
 }
+
+// the 64-bit row tables and the int2 chunk lists of the multi-tensor kernels: 8-byte aligned (include/dasac_hip.h)
+static bool rows_aligned(const void* tensors, const void* chunks) { return (((uintptr_t)tensors | (uintptr_t)chunks) & 7) == 0; }
 
 static SgdGroups sgd_groups(const float* group_lr, const float* group_wd, int n_groups) {
   SgdGroups hp;
@@ -968,6 +973,7 @@ static int launch_sgd(const void* tensors, const int32_t* chunks, int n_chunks, 
 extern "C" int dasac_sgd_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_lr,
                               const float* group_wd, int n_groups, float momentum, int first, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_step: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "sgd_step: misaligned row table / chunk list");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_step: 1..8 parameter groups");
   return launch_sgd<false, false>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, nullptr, 0, stream);
 }
@@ -976,6 +982,7 @@ extern "C" int dasac_sgd_nesterov_step(const void* tensors, int n_tensors, const
                                        const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
                                        dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_nesterov_step: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "sgd_nesterov_step: misaligned row table / chunk list");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_nesterov_step: 1..8 parameter groups");
   DASAC_REQUIRE(momentum > 0.f, "sgd_nesterov_step: Nesterov momentum requires a momentum");
   return launch_sgd<true, false>(tensors, chunks, n_chunks, sgd_groups(group_lr, group_wd, n_groups), momentum, first, nullptr, 0, stream);
@@ -989,6 +996,7 @@ extern "C" int dasac_sgd_step_ctl(const void* tensors, int n_tensors, const int3
                                   const float* group_wd, int n_groups, float momentum, int first, const void* ctl, int apply_coef,
                                   int honour_skip, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_step_ctl: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "sgd_step_ctl: misaligned row table / chunk list");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_step_ctl: 1..8 parameter groups");
   DASAC_REQUIRE(first >= -1 && first <= 1, "sgd_step_ctl: first is 0, 1 or -1 (per row)");
   DASAC_REQUIRE(ctl_args_ok(ctl, apply_coef, honour_skip), "sgd_step_ctl: a 16-byte aligned control block and 0/1 flags");
@@ -1000,6 +1008,7 @@ extern "C" int dasac_sgd_nesterov_step_ctl(const void* tensors, int n_tensors, c
                                            const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
                                            const void* ctl, int apply_coef, int honour_skip, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_lr && group_wd && n_tensors > 0 && n_chunks > 0, "sgd_nesterov_step_ctl: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "sgd_nesterov_step_ctl: misaligned row table / chunk list");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "sgd_nesterov_step_ctl: 1..8 parameter groups");
   DASAC_REQUIRE(momentum > 0.f, "sgd_nesterov_step_ctl: Nesterov momentum requires a momentum");
   DASAC_REQUIRE(first >= -1 && first <= 1, "sgd_nesterov_step_ctl: first is 0, 1 or -1 (per row)");
@@ -1029,6 +1038,7 @@ static int launch_adam(const void* tensors, const int32_t* chunks, int n_chunks,
 extern "C" int dasac_adam_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks, const float* group_wd,
                                int n_groups, double beta1, double beta2, double eps, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_wd && n_tensors > 0 && n_chunks > 0, "adam_step: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "adam_step: misaligned row table / chunk list");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "adam_step: 1..8 parameter groups");
   DASAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adam_step: betas in [0, 1), eps >= 0");
   return launch_adam<false>(tensors, chunks, n_chunks, group_wd, n_groups, beta1, beta2, eps, nullptr, 0, stream);
@@ -1038,6 +1048,7 @@ extern "C" int dasac_adam_step_ctl(const void* tensors, int n_tensors, const int
                                    int n_groups, double beta1, double beta2, double eps, const void* ctl, int apply_coef,
                                    int honour_skip, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && group_wd && n_tensors > 0 && n_chunks > 0, "adam_step_ctl: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "adam_step_ctl: misaligned row table / chunk list");
   DASAC_REQUIRE(n_groups >= 1 && n_groups <= 8, "adam_step_ctl: 1..8 parameter groups");
   DASAC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0, "adam_step_ctl: betas in [0, 1), eps >= 0");
   DASAC_REQUIRE(ctl_args_ok(ctl, apply_coef, honour_skip), "adam_step_ctl: a 16-byte aligned control block and 0/1 flags");
@@ -1050,6 +1061,7 @@ extern "C" size_t dasac_grad_norm_workspace(int n_chunks) { return n_chunks > 0 
 extern "C" int dasac_grad_norm(const void* tensors, int row_bytes, int n_tensors, const int32_t* chunks, int n_chunks, float max_norm,
                                void* workspace, size_t workspace_bytes, void* ctl, int64_t* skipped, dasac_stream_t stream) {
   DASAC_REQUIRE(tensors && chunks && workspace && ctl && n_tensors > 0 && n_chunks > 0, "grad_norm: bad arguments");
+  DASAC_REQUIRE(rows_aligned(tensors, chunks), "grad_norm: misaligned row table / chunk list");
   DASAC_REQUIRE(row_bytes == (int)sizeof(SgdTensor) || row_bytes == (int)sizeof(AdamTensor),
                 "grad_norm: row_bytes names the table, 48 (dasac_sgd_step) or 64 (dasac_adam_step)");
   DASAC_REQUIRE(workspace_bytes >= dasac_grad_norm_workspace(n_chunks) && ((uintptr_t)workspace & 7) == 0, "grad_norm: workspace too small");

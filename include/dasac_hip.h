@@ -11,6 +11,11 @@
  * Conventions (all entry points):
  *   - plain device pointers + sizes; NCHW contiguous fp32 activations / weights, int64 labels
  *     (255 = ignore), bool masks as uint8;  no torch types anywhere in a signature;
+ *   - an OPERAND (activation, weight, gradient, label, image, bit mask, packed GEMM operand) needs the alignment of its
+ *     element and no more, and the result does not depend on where it lies; only what the text of an entry names needs more:
+ *     control blocks and workspaces, the dasac_conv_gemm_batched strides, and the DESCRIPTOR tables the kernels read as 16- or
+ *     8-byte records (gather tables; job, pair and row tables; chunk lists).  A descriptor off its alignment is DASAC_EINVAL
+ *     before any launch;
  *   - `stream` is a hipStream_t (NULL = the legacy default stream);
  *   - return 0 on success, a negative DASAC_E* code otherwise; never throws, never allocates
  *     device memory, never synchronises the stream.  Scratch comes from the caller:
@@ -74,6 +79,8 @@ int dasac_pseudo_labels(const float* probs, const uint8_t* ignore, const float* 
  *   weights of one GEMM must use the same order.
  * dasac_conv_table   builds the gather table [Kpad][4] int32 for planes of plane_h x plane_w;
  *                    transposed=1 gives the data-gradient geometry (C = Cout, dh = pad - kh*dil).
+ *                    The table is read one 16-byte row at a time: `table` must be 16-byte aligned here and in every entry
+ *                    that takes it (dasac_conv_gemm, _stats, _x3, _batched, dasac_conv_wgrad, _x3).
  * dasac_conv_pack    lays W [Cout,Cin,kh,kw] out as the k-interleaved [Kpad/4][Mpad][4] GEMM operand
  *                    (transposed=1: rows (tap,co), columns ci), optionally scaled per co by
  *                    `scale` = folded BN gamma*invstd -- forward and data-gradient both contract
@@ -145,7 +152,9 @@ int dasac_conv_gemm_batched(const float* x, const float* packed, const int32_t* 
  * 2^-17; the dropped tail*tail term is below 2^-16).  The activations are split inside the kernel
  * (NCHW fp32 in HBM, nothing else changes), the weights once by dasac_conv_pack_x3 from the output of
  * dasac_conv_pack (same byte size).  Same table, epilogue, workspace and schedule as dasac_conv_gemm;
- * M must exceed 32.  Opt-in: the host picks it per call (DASAC_PRECISION=bf16x3 in the Python layer). */
+ * M must exceed 32.  Opt-in: the host picks it per call (DASAC_PRECISION=bf16x3 in the Python layer).
+ * dasac_conv_pack_x3 reads `packed` and writes `packed_x3` (which may be `packed` itself) through 4-byte-aligned vectors:
+ * both need element alignment only. */
 int dasac_conv_pack_x3(const float* packed, int M, int K, void* packed_x3, dasac_stream_t stream);
 int dasac_conv_gemm_x3(const float* x, const void* packed_x3, const int32_t* table, float* out,
                        int Nb, int Cx, int H, int W, int OH, int OW, int stride, int M, int K,
@@ -376,7 +385,8 @@ int dasac_class_state(float* running_conf, const double* class_sums, int B, int6
  *     update = 0 writes no slow tensor; out[0] is the same distance either way.
  *     `pairs`: device array of {const float* fast; float* slow; int64 n}; `chunks`: device (tensor, chunk) int32 pairs of
  *     dasac_ema_chunk_elems() elements, SORTED by tensor; `sq`: scratch of n_tensors + n_chunks doubles (one partial per
- *     chunk, added per tensor in a fixed order: the result is bit-identical from run to run).
+ *     chunk, added per tensor in a fixed order: the result is bit-identical from run to run).  `pairs`, `chunks` and `sq`
+ *     must be 8-byte aligned (64-bit fields, int32 pairs read as one word); the tensors they point to need element alignment.
  * dasac_scale_planes     Dropout2d with an explicit per-(n,c) keep mask (fcn.py:52,56).
  */
 int dasac_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,
@@ -396,7 +406,9 @@ int dasac_ema_chunk_elems(void);
  * (base_trainer.py:63-66 over basenet.py:73-95):  d = g + wd*p; buf = first ? d : momentum*buf + d; p -= lr*buf.
  * tensors: device array of {float* p; const float* g; const float* g2 (NULL or a second gradient, summed as g2 + g before
  * anything else -- what two backward passes would have accumulated into .grad); float* buf; int64 n; int64 group}; chunks as for
- * dasac_ema_update ((tensor, chunk) pairs of dasac_ema_chunk_elems() elements); group_lr/group_wd: HOST arrays. */
+ * dasac_ema_update ((tensor, chunk) pairs of dasac_ema_chunk_elems() elements); group_lr/group_wd: HOST arrays.
+ * `tensors` and `chunks` must be 8-byte aligned, here and in dasac_sgd_nesterov_step, dasac_adam_step, dasac_grad_norm and the
+ * _ctl forms; p, g, g2 and the state tensors may lie at any 4-byte phase (the bits do not depend on it). */
 int dasac_sgd_step(const void* tensors, int n_tensors, const int32_t* chunks, int n_chunks,
                    const float* group_lr, const float* group_wd, int n_groups, float momentum, int first,
                    dasac_stream_t stream);
@@ -576,7 +588,8 @@ int dasac_bn_bwd_apply(const float* dy, const float* z, const float* mean, const
  * dasac_conv_pack calls per step did, in two launches.  `jobs` are DEVICE arrays of the structs below, `chunks` device
  * (job, chunk) int32 pairs: one chunk = 256 channels of a fold job / dasac_pack_chunk_elems() floats of a pack job's output
  * (ceil(Kpad*Mpad / chunk) chunks per job; K and M padding are written as zeros).  Single-branch convolutions only
- * (taps = kh*kw of the one branch); mode / order as in dasac_conv_pack, Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K). */
+ * (taps = kh*kw of the one branch); mode / order as in dasac_conv_pack, Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K).
+ * `jobs` and `chunks` must be 8-byte aligned; the tensors a job points to need element alignment. */
 typedef struct dasac_fold_job {
   const float *gamma, *beta, *mean, *var, *conv_bias; /* conv_bias may be NULL */
   float *scale, *shift, *invstd;                      /* all three are written: invstd is NOT optional here */
