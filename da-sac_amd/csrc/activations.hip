@@ -49,17 +49,6 @@ __device__ __forceinline__ float act_load1(act_gptr plane, unsigned i) {
   return *reinterpret_cast<const float __attribute__((address_space(1)))*>(plane + i * 4u);
 }
 
-__device__ __forceinline__ double act_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double act_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 struct ActAcc {
   double sum = 0, sumsq = 0;
   float maxabs = 0.f;
@@ -117,9 +106,9 @@ __global__ __launch_bounds__(kActBlock) void activation_stats_planes(const ActTe
       for (int i = 4 * quads; i < n; ++i) act_take(a, act_load1(x, i), i);
   }
   __shared__ double red[kActBlock / kWave][kActCols];
-  const double s = wave_sum(a.sum), sq = wave_sum(a.sumsq), mx = act_wave_max((double)a.maxabs);
+  const double s = wave_sum(a.sum), sq = wave_sum(a.sumsq), mx = wave_max((double)a.maxabs);
   const double nf = wave_sum((double)a.nonfinite), zr = wave_sum((double)a.zeros);
-  const double fi = act_wave_min(a.first == INT_MAX ? kActNone : (double)a.first);
+  const double fi = wave_min(a.first == INT_MAX ? kActNone : (double)a.first);
   if ((threadIdx.x & 63) == 0) {
     double* r = red[threadIdx.x >> 6];
     r[0] = s, r[1] = sq, r[2] = mx, r[3] = nf, r[4] = fi, r[5] = zr;
@@ -158,7 +147,7 @@ __global__ __launch_bounds__(kWave) void activation_stats_finish(const ActTensor
     }
   }
   s = wave_sum(s), sq = wave_sum(sq), nf = wave_sum(nf), zr = wave_sum(zr);
-  mx = act_wave_max(mx), first = act_wave_min(first);
+  mx = wave_max(mx), first = wave_min(first);
   if (threadIdx.x == 0) {
     double* out = table + ((size_t)seg * R + row) * kActCols;
     out[0] = s, out[1] = sq, out[2] = mx, out[3] = nf, out[4] = first < kActNone ? first : 0.0, out[5] = zr;

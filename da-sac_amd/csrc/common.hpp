@@ -88,5 +88,29 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// The fixed-order sum over a 256-thread block: wave butterflies, lane 0 of each wave to LDS, (r0 + r1) + (r2 + r3).  Run-to-run
+// determinism and every "bit for bit" test of the reductions rest on this order.  The sum is valid in EVERY thread after the call
+// (a caller that uses it in thread 0 only leaves the LDS reads to that thread).  One call per kernel: the slots are not guarded
+// against a second one.  The (s, q) pair form of the train-mode BatchNorm kernels and the one-column-per-thread form with max and
+// min columns (tensor_stats_chunks, activation_stats_planes) keep the same order written out: on a shared helper each of them
+// compiled to another instruction stream (profiles/pointwise_split.md).
+__device__ __forceinline__ double block_sum(double v) {
+  __shared__ double r[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (r[0] + r[1]) + (r[2] + r[3]);
+}
 
 }  // namespace dasac

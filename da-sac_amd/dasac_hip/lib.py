@@ -223,6 +223,11 @@ def require_gpu(*tensors):
                 raise known
 
 
+def chunk_list(sizes, chunk):
+    """The (tensor id, chunk index) list of the multi-tensor kernels, sorted by tensor id: a host int32 [n, 2] tensor."""
+    return torch.tensor([(i, j) for i, n in enumerate(sizes) for j in range((n + chunk - 1) // chunk)], dtype=torch.int32).reshape(-1, 2)
+
+
 _ws_cache = {}
 
 

@@ -813,23 +813,21 @@ def build_refresh_tables(fold_jobs, pack_jobs, device):
     assert fold_dt.itemsize == 72 and pack_dt.itemsize == 56
     keep = []
     fj = np.zeros(len(fold_jobs), dtype=fold_dt)
-    fchunks = []
     for i, (g, b, m, v, cb, outs, eps, C) in enumerate(fold_jobs):
         L.require_gpu(g, b, m, v, cb, *outs)
         fj[i] = (g.data_ptr(), b.data_ptr(), m.data_ptr(), v.data_ptr(), 0 if cb is None else cb.data_ptr(), outs[0].data_ptr(),
                  outs[1].data_ptr(), outs[2].data_ptr(), float(eps), int(C))
-        fchunks += [(i, c) for c in range((C + 255) // 256)]
         keep.append(outs)
     pj = np.zeros(len(pack_jobs), dtype=pack_dt)
-    pchunks, chunk = [], lib.dasac_pack_chunk_elems()
     for i, (w, sc, out, Cout, Cin, taps, Mpad, Kpad, mode, order) in enumerate(pack_jobs):
         L.require_gpu(w, sc, out)
         assert w.is_contiguous() and out.is_contiguous() and out.numel() == Kpad * Mpad
         pj[i] = (w.data_ptr(), 0 if sc is None else sc.data_ptr(), out.data_ptr(), Cout, Cin, taps, Mpad, Kpad, mode, order, 0)
-        pchunks += [(i, c) for c in range((Kpad * Mpad + chunk - 1) // chunk)]
         keep.append(out)
+    fchunks = L.chunk_list([int(job[7]) for job in fold_jobs], 256)      # 256 channels of a fold job per block
+    pchunks = L.chunk_list([job[7] * job[6] for job in pack_jobs], lib.dasac_pack_chunk_elems())      # of Kpad * Mpad elements
     up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).to(device) if a.size else None
-    upi = lambda l: torch.tensor(l, dtype=torch.int32).reshape(-1, 2).to(device) if l else None
+    upi = lambda t: t.to(device) if len(t) else None
     return {"fold": up(fj), "fold_chunks": upi(fchunks), "n_fold_chunks": len(fchunks),
             "pack": up(pj), "pack_chunks": upi(pchunks), "n_pack_chunks": len(pchunks), "keep": keep}
 
@@ -996,17 +994,15 @@ class EmaPlan:
         lib = L.load()
         L.require_gpu(*fast_tensors)
         L.require_gpu(*slow_tensors)
-        chunk = lib.dasac_ema_chunk_elems()
         pairs = np.zeros((len(fast_tensors), 3), dtype=np.int64)
-        chunks = []
         for i, (f, s) in enumerate(zip(fast_tensors, slow_tensors)):
             assert f.is_contiguous() and s.is_contiguous() and f.numel() == s.numel() and f.dtype == torch.float32
             pairs[i] = (f.data_ptr(), s.data_ptr(), f.numel())
-            chunks += [(i, j) for j in range((f.numel() + chunk - 1) // chunk)]
+        chunks = L.chunk_list([f.numel() for f in fast_tensors], lib.dasac_ema_chunk_elems())
         dev = fast_tensors[0].device
         self.key = tuple(int(v) for v in pairs[:, :2].reshape(-1))
         self.pairs = torch.from_numpy(pairs).to(dev)
-        self.chunks = torch.tensor(chunks, dtype=torch.int32).to(dev)
+        self.chunks = chunks.to(dev)
         self.sq = torch.empty(len(fast_tensors) + len(chunks), dtype=torch.float64, device=dev)   # per-tensor sums + chunk partials
         self.n_tensors, self.n_chunks = len(fast_tensors), len(chunks)
         self.slow = list(slow_tensors)

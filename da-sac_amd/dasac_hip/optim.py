@@ -247,13 +247,12 @@ class _FusedOptimizer(torch.optim.Optimizer):
         row_of: None, or the int32 host array of dasac_tensor_stats, uploaded with them."""
         ent = self._tables.get(slot)
         if ent is None or ent[0] != key:
-            chunk = L.load().dasac_ema_chunk_elems()
-            chunks = [(i, j) for i, n in enumerate(sizes) for j in range((n + chunk - 1) // chunk)]
+            chunks = L.chunk_list(sizes, L.load().dasac_ema_chunk_elems())
             # The gradients are fresh allocations every step, so this table is rebuilt every step: upload it through pinned
             # memory without blocking.  A pageable source makes `.to(device)` wait for the WHOLE stream -- the backward pass
             # still running on the device -- and the device then idles while the host catches up (measured: ~3 ms per step).
             up = lambda a: torch.from_numpy(a).pin_memory().to(device, non_blocking=True)
-            ent = (key, up(rows), up(np.asarray(chunks, dtype=np.int32).reshape(-1, 2)), len(sizes), len(chunks),
+            ent = (key, up(rows), chunks.pin_memory().to(device, non_blocking=True), len(sizes), len(chunks),
                    None if row_of is None else up(row_of))
             self._tables[slot] = ent
         return ent

@@ -1,4 +1,4 @@
-"""Train-mode BatchNorm kernels (pointwise.hip: bn_stats, bn_sums_finish, bn_tile_stats_reduce, bn_train_finalize, bn_apply,
+"""Train-mode BatchNorm kernels (batchnorm.hip: bn_stats, bn_sums_finish, bn_tile_stats_reduce, bn_train_finalize, bn_apply,
 bn_apply_tiles, bn_bwd_reduce, bn_bwd_apply, bn_bwd_apply_partials, bn_bwd_params) on their own, against float64 ATen
 `F.batch_norm(training=True)` + autograd on the CPU.
 

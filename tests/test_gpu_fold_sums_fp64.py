@@ -1,4 +1,4 @@
-"""The frozen-BN helpers of pointwise.hip -- bn_fold, bn_fold_multi, bn_param_grads, channel_sums -- against float64 on the CPU,
+"""The frozen-BN helpers of batchnorm.hip -- bn_fold, bn_fold_multi, bn_param_grads, channel_sums -- against float64 on the CPU,
 from the formulas of include/dasac_hip.h.  Bounds are per element and relative to the terms each value is made of (as in
 test_gpu_bn_kernels.py), never to the tensor's max, and come from first-order rounding analysis: one u = 2^-24 per correctly
 rounded fp32 operation, then doubled.  They assume -ffp-contract=off and correctly rounded divide and sqrt.

@@ -1,4 +1,4 @@
-"""Max pooling (csrc/pointwise.hip) against float64 ATen on the CPU, exactly, through dasac_hip.ops.
+"""Max pooling (csrc/pool.hip) against float64 ATen on the CPU, exactly, through dasac_hip.ops.
 
 Forward: selecting a maximum rounds nothing, so F.max_pool2d(x.double(), ..., return_indices=True) is the reference for y bit for
 bit, and its indices for the argmax code: flat = (oh*s - p + code // k) * W + (ow*s - p + code % k).  ATen takes the first maximum
@@ -43,16 +43,16 @@ from fp64_yardstick import _ratio, _report
 
 pytestmark = pytest.mark.gpu
 K_NUM_CU = 256              # common.hpp kNumCu
-SIGN_MAX_K = 11             # pointwise.hip kPoolSignMaxK
+SIGN_MAX_K = 11             # pool.hip kPoolSignMaxK
 
 
 def _fwd_kernel(k, s):
-    """dasac_maxpool_fwd's dispatch (pointwise.hip)"""
+    """dasac_maxpool_fwd's dispatch (pool.hip)"""
     return {(3, 2): "fwd_quad<3,2>", (2, 2): "fwd_quad<2,2>", (3, 1): "fwd<3,1>"}.get((k, s), "fwd<0,0>")
 
 
 def _bwd_kernel(k, s, p):
-    """dasac_maxpool_bwd's dispatch (pointwise.hip)"""
+    """dasac_maxpool_bwd's dispatch (pool.hip)"""
     if (k, s, p) == (3, 2, 1):
         return "bwd_3s2p1"
     return {(3, 2): "bwd<3,2>", (2, 2): "bwd<2,2>", (3, 1): "bwd<3,1>"}.get((k, s), "bwd<0,0>")
@@ -206,7 +206,7 @@ def test_maxpool_second_pass_of_the_capped_grid(case):
     k, s, p, ceil, planes, H, W = case
     OH, OW = ops.pool_out(H, k, s, p, ceil), ops.pool_out(W, k, s, p, ceil)
     threads = _default_cap() * 256
-    # the item counts of the two launchers (pointwise.hip: items4 / total in dasac_maxpool_fwd, items2 / items in dasac_maxpool_bwd)
+    # the item counts of the two launchers (pool.hip: items4 / total in dasac_maxpool_fwd, items2 / items in dasac_maxpool_bwd)
     fwd_items = planes * OH * ((OW + 3) // 4) if _fwd_kernel(k, s).startswith("fwd_quad") else planes * OH * OW
     bwd_items = planes * ((H + 1) // 2) * ((W + 3) // 4) if _bwd_kernel(k, s, p) == "bwd_3s2p1" else planes * H * ((W + 3) // 4)
     assert fwd_items > threads and bwd_items > threads and planes * H * W < 20e6

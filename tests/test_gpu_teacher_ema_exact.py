@@ -1,4 +1,4 @@
-"""The momentum-teacher update (pointwise.hip: ema_chunks, ema_tensor_sums, ema_finish; ops.EmaPlan) bit for bit.
+"""The momentum-teacher update (optim.hip: ema_chunks, ema_tensor_sums, ema_finish; ops.EmaPlan) bit for bit.
 
 Reference, on the CPU in plain torch: `slow.mul_(m).add_(fast * (1.0 - m))` in fp32 (oracle.head_ref.momentum_update's line:
 three roundings, the factors fl32(m) and fl32(1 - m) with the difference taken in DOUBLE), and for the returned distance

@@ -115,7 +115,7 @@ HEAD = {
 POOL = {"maxpool_bwd_3s2p1": (64, 0, 200)}                    # 2 x 4 pixels per thread: ~170 VALU per 8 pixels (306 per 4 before)
 
 
-@pytest.mark.parametrize("src,table", [("head", HEAD), ("pointwise", POOL)])
+@pytest.mark.parametrize("src,table", [("head", HEAD), ("pool", POOL)])
 def test_streaming_head_kernels_keep_their_registers_and_instruction_counts(tmp_path, src, table):
     txt = _asm(tmp_path, src)
     meta = _kernel_meta(txt)
