@@ -16,18 +16,15 @@
 // Index arithmetic lives in winograd_index.hpp and is walked on the host by tools/winograd_index_check.cpp.  Every global access
 // goes through a buffer descriptor of the tensor's exact extent with the whole offset in the per-lane operand (the scalar
 // offset is not range checked by the hardware): an offset past the extent reads zero / stores nothing.
-#include "common.hpp"
+#include "conv_common.hpp"
 #include "winograd_index.hpp"
 
 namespace dasac {
 namespace wino {
 
-constexpr int kRsrcFlags = 0x00020000;   // raw buffer, 32-bit data format (as conv_igemm.hip)
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, kRsrcFlags);
-}
+// (make_rsrc: conv_common.hpp)
 __device__ __forceinline__ float ld(__amdgpu_buffer_rsrc_t r, unsigned voff) {
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
 }
@@ -111,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void input_transform(const float* __restric
 
 // ---- output transform ------------------------------------------------------------------------------------------------------
 // grid (ceil(N*H*W / 256), M): one thread per OUTPUT element, lanes along the flattened (n, y, x) pixel index -- the pixel axis of
-// the ReLU bit masks (conv_igemm.hip Epilogue: bits[m][pix >> 5] bit pix & 31), so a wave ballot is two mask words, as in the
+// the ReLU bit masks (conv_gemm.hip Epilogue: bits[m][pix >> 5] bit pix & 31), so a wave ballot is two mask words, as in the
 // direct epilogue.  Output (ey, ex) of a tile is sum_j sum_k sy_j sx_k Y[ey + j][ex + k], signs (+,+,+) for e = 0 and (+,-,-)
 // for e = 1 (A^T = [[1,1,1,0],[0,1,-1,-1]]): nine loads; the four outputs of a tile re-read its values from cache.
 // BITS: 0 none, 1 record (v > 0 after the ReLU), 2 mask (v = bit ? v : 0).

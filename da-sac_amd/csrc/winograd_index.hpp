@@ -141,7 +141,7 @@ DASAC_HD unsigned patch_offset(const Geom& g, int C, int n, int c, int y0, int x
 DASAC_HD unsigned point_offset(const Geom& g, int C, int pt, int c, int tile) { return (unsigned)((pt * C + c) * g.T + tile) * 4u; }
 // byte offset into an NCHW activation of M channels
 DASAC_HD unsigned out_offset(const Geom& g, int M, int n, int m, int rem) { return (unsigned)((n * M + m) * g.HW + rem) * 4u; }
-// largest tensor the 32-bit byte offsets reach (the limit of conv_igemm.hip)
+// largest tensor the 32-bit byte offsets reach (kMaxTensorBytes of conv_common.hpp)
 constexpr int64_t kMaxBytes = (1ll << 32) - 4096;
 
 }  // namespace wino

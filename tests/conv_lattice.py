@@ -294,7 +294,7 @@ def winograd_emulate(x, w, dilation, scale=None):
 
 
 # ----------------------------------------------------------------------------------------------
-# split-bf16: head = bf16(x) (round to nearest even), tail = bf16(x - head), as split_bf16 of csrc/conv_igemm.hip
+# split-bf16: head = bf16(x) (round to nearest even), tail = bf16(x - head), as split_bf16 of csrc/conv_common.hpp
 # ----------------------------------------------------------------------------------------------
 def bf16_round(a):
     u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)

@@ -23,7 +23,7 @@ SEEDS = (1, 2)            # the seeds both test modules use; test_engine_plans_c
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the kernel-choice rules of csrc/conv_igemm.hip, restated on the host (test_engine_plans_cpu.py compares them with the library)
+# the kernel-choice rules of csrc/conv_gemm.hip and csrc/conv_wgrad.hip, restated on the host (test_engine_plans_cpu.py compares them with the library)
 # ---------------------------------------------------------------------------------------------------------------
 def mpad(M):
     return (M + 127) // 128 * 128 if M > 64 else (64 if M > 32 else 32)

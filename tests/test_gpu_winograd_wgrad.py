@@ -1,5 +1,5 @@
 """Winograd F(2x2,3x3) weight gradient of the wide dilated 3x3 convolutions (csrc/winograd.hip grad_transform / wgrad_finish around
-conv_wgrad_batched of csrc/conv_igemm.hip; ops.winograd_wgrad): accuracy against float64 ATen with the direct path as the yardstick,
+conv_wgrad_batched of csrc/conv_wgrad.hip; ops.winograd_wgrad): accuracy against float64 ATen with the direct path as the yardstick,
 bit-exactness on the summable lattice, the routing predicate's refusals and the engine routing on one layer4-shaped bottleneck.
 Shapes are the smallest that reach every way to go wrong: both channel orientations (M and K swapped), dilations 1, 2 and 4 on
 11 x 9 and 13 x 10 maps (unequal phases, tiles that hang over both edges), tile counts that are no multiple of the 32-pixel K-step

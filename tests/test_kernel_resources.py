@@ -78,9 +78,10 @@ def _loops(lines):
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_hot_gemm_loops_have_no_scratch_fit_their_occupancy_and_keep_their_instruction_diet(tmp_path):
-    txt = _asm(tmp_path, "conv_igemm")
-    meta = _kernel_meta(txt)
+    asm = {src: _asm(tmp_path, src) for src in ("conv_gemm", "conv_wgrad")}      # the file a kernel lives in is named after it
     for key, (vgpr_budget, scratch_budget, diet) in HOT.items():
+        txt = asm[key[:key.index("IL")]]
+        meta = _kernel_meta(txt)
         names = [n for n in meta if key in n]
         assert len(names) == 1, (key, names)
         scratch, vgprs, _ = meta[names[0]]

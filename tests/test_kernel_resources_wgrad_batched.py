@@ -1,4 +1,4 @@
-"""Register / scratch budget of the batched weight-gradient kernel (conv_wgrad_batched of csrc/conv_igemm.hip), the budget of its
+"""Register / scratch budget of the batched weight-gradient kernel (conv_wgrad_batched of csrc/conv_wgrad.hip), the budget of its
 siblings in test_kernel_resources.py: at most 168 VGPRs (3 waves per SIMD), at most 64 bytes of scratch, and no scratch
 instruction or SGPR spill (v_readlane / v_writelane) inside a loop that carries MFMAs.  Cross-compiles to gfx950 assembly; no GPU."""
 import os
@@ -13,7 +13,7 @@ KERNEL = "conv_wgrad_batched"
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")
 def test_batched_weight_gradient_kernel_fits_its_occupancy_and_keeps_its_mfma_loop_free_of_spills(tmp_path):
-    txt = _asm(tmp_path, "conv_igemm")
+    txt = _asm(tmp_path, "conv_wgrad")
     meta = _kernel_meta(txt)
     names = [n for n in meta if KERNEL in n]
     assert len(names) == 1, names
