@@ -253,6 +253,172 @@ __global__ __launch_bounds__(kBlock) void wgrad_finish(const float* __restrict__
   }
 }
 
+// ---- weight gradient as F(4x4,3x3) -------------------------------------------------------------------------------------------
+// The same adjoint with four outputs per tile and axis: 36 point products per 4x4 output tile where F(2x2) spends 4 x 16, and
+// transformed tensors [36][C][T] of 0.59 times the size.  Evaluation points 0, 1, -1, 2, -1/2, inf, chosen for the weight gradient's
+// error against float64 (profiles/EXPERIMENTS.md); the three matrices, B^T scaled to integers and G carrying the inverse factors:
+//   B^T = [[2,3,-4,-3,2,0],[0,2,5,1,-2,0],[0,2,1,-5,2,0],[0,-1,-2,1,2,0],[0,-2,1,2,-1,0],[0,2,3,-4,-3,2]]
+//   A   = [[1,0,0,0],[1,1,1,1],[1,-1,1,-1],[1,2,4,8],[1,-1/2,1/4,-1/8],[0,0,0,1]]
+//   G   = [[1/2,0,0],[1/6,1/6,1/6],[1/6,-1/6,1/6],[1/30,1/15,2/15],[16/15,-8/15,4/15],[0,0,1/2]]
+// (tests/winograd4_ref.py holds them as fractions and checks the identities in float64).  Only the weight gradient runs in this form:
+// the forward and the data gradient feed ReLU patterns and stay F(2x2).  The kernels are the twins of the F(2x2) ones above --
+// one thread per (channel, tile), lanes along tiles, exact-extent descriptors -- and additionally write the padding tiles
+// (Geom::T is rounded up to a multiple of 4) as zeros at all 36 points.
+__device__ __forceinline__ void bt6(float d0, float d1, float d2, float d3, float d4, float d5, float (&o)[6]) {
+  o[0] = (2.f * (d0 + d4) + 3.f * (d1 - d3)) - 4.f * d2;
+  o[1] = (2.f * (d1 - d4) + 5.f * d2) + d3;
+  o[2] = (2.f * (d1 + d4) + d2) - 5.f * d3;
+  o[3] = (d3 - d1) + 2.f * (d4 - d2);
+  o[4] = 2.f * (d3 - d1) + (d2 - d4);
+  o[5] = (2.f * (d1 + d5) + 3.f * (d2 - d4)) - 4.f * d3;
+}
+__device__ __forceinline__ void a6(float y0, float y1, float y2, float y3, float (&o)[6]) {
+  o[0] = y0;
+  o[1] = (y0 + y2) + (y1 + y3);
+  o[2] = (y0 + y2) - (y1 + y3);
+  o[3] = (y0 + 4.f * y2) + (2.f * y1 + 8.f * y3);
+  o[4] = (y0 + 0.25f * y2) - (0.5f * y1 + 0.125f * y3);
+  o[5] = y3;
+}
+__device__ __forceinline__ void gt3(float p0, float p1, float p2, float p3, float p4, float p5, float (&o)[3]) {
+  constexpr float k6 = 1.f / 6.f, k15 = 1.f / 15.f, k30 = 1.f / 30.f;
+  o[0] = (0.5f * p0 + k6 * (p1 + p2)) + (k30 * p3 + (16.f * k15) * p4);
+  o[1] = k6 * (p1 - p2) + (k15 * p3 - (8.f * k15) * p4);
+  o[2] = (k6 * (p1 + p2) + 0.5f * p5) + ((2.f * k15) * p3 + (4.f * k15) * p4);
+}
+
+// grid (ceil(T / 256), C).  V = B^T d B of the 6x6 patch (taps `dilation` apart), 36 stores.
+__global__ __launch_bounds__(kBlock) void input_transform4(const float* __restrict__ X, float* __restrict__ V, Geom g, int C,
+                                                            unsigned x_bytes, unsigned v_bytes) {
+  const int tile = blockIdx.x * kBlock + threadIdx.x;
+  if (tile >= g.T) return;
+  const int c = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t rx = make_rsrc(X, x_bytes), rv = make_rsrc(V, v_bytes);
+  if (!real_tile(g, tile)) {
+#pragma unroll
+    for (int pt = 0; pt < 36; ++pt) st(rv, point_offset(g, C, pt, c, tile), 0.f);
+    return;
+  }
+  int n, y0, x0;
+  tile_origin<4>(g, tile, n, y0, x0);
+  float t[6][6];                                           // B^T d, a column of the patch at a time
+#pragma unroll
+  for (int kx = 0; kx < 6; ++kx) {
+    float d[6], o[6];
+#pragma unroll
+    for (int ky = 0; ky < 6; ++ky) d[ky] = ld(rx, patch_offset(g, C, n, c, y0, x0, ky, kx));
+    bt6(d[0], d[1], d[2], d[3], d[4], d[5], o);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) t[a][kx] = o[a];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    float v[6];
+    bt6(t[a][0], t[a][1], t[a][2], t[a][3], t[a][4], t[a][5], v);
+#pragma unroll
+    for (int b = 0; b < 6; ++b) st(rv, point_offset(g, C, a * 6 + b, c, tile), v[b]);
+  }
+}
+
+// grid (ceil(T / 256), M).  dM = A dY A^T of the tile's 4x4 output pixels; output (ey, ex) is tap (ey + 1, ex + 1) of the tile's
+// patch, so the overhang of a tile past the map edge takes patch_offset's zero.
+__global__ __launch_bounds__(kBlock) void grad_transform4(const float* __restrict__ dY, float* __restrict__ dM, Geom g, int M,
+                                                           unsigned y_bytes, unsigned m_bytes) {
+  const int tile = blockIdx.x * kBlock + threadIdx.x;
+  if (tile >= g.T) return;
+  const int m = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t ry = make_rsrc(dY, y_bytes), rm = make_rsrc(dM, m_bytes);
+  if (!real_tile(g, tile)) {
+#pragma unroll
+    for (int pt = 0; pt < 36; ++pt) st(rm, point_offset(g, M, pt, m, tile), 0.f);
+    return;
+  }
+  int n, y0, x0;
+  tile_origin<4>(g, tile, n, y0, x0);
+  float t[6][4];                                           // A dY
+#pragma unroll
+  for (int ex = 0; ex < 4; ++ex) {
+    float d[4], o[6];
+#pragma unroll
+    for (int ey = 0; ey < 4; ++ey) d[ey] = ld(ry, patch_offset(g, M, n, m, y0, x0, ey + 1, ex + 1));
+    a6(d[0], d[1], d[2], d[3], o);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) t[a][ex] = o[a];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    float v[6];
+    a6(t[a][0], t[a][1], t[a][2], t[a][3], v);
+#pragma unroll
+    for (int b = 0; b < 6; ++b) st(rm, point_offset(g, M, a * 6 + b, m, tile), v[b]);
+  }
+}
+
+// P [splits][36][M][C], Psum [splits][M] (channel sums of point (1,1) of dM, whose row of A is all ones = sum of dz) -> dW, dot and
+// sum_dz as wgrad_finish leaves them.  Same grid, thread roles and summation order; 36 points, G^T (.) G from 6x6 to 3x3.
+__global__ __launch_bounds__(kBlock) void wgrad_finish4(const float* __restrict__ P, const float* __restrict__ Psum, int splits, int M,
+                                                         int C, const float* __restrict__ Wt, const float* __restrict__ scale,
+                                                         float* __restrict__ dW, float* __restrict__ dot, float* __restrict__ sum_dz,
+                                                         unsigned p_bytes, unsigned w_bytes) {
+  const int co = blockIdx.y, ci0 = blockIdx.x * 64;
+  const int tx = threadIdx.x, c = tx & 63, q = tx >> 6;
+  const __amdgpu_buffer_rsrc_t rp = make_rsrc(P, p_bytes), rw = make_rsrc(Wt, w_bytes), rd = make_rsrc(dW, w_bytes);
+  if (sum_dz && blockIdx.x == 0 && q == 0) {                 // one wave: the splits' channel sums in parallel
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(Psum, (unsigned)(splits * M) * 4u);
+    float sv = 0.f;
+    for (int s = c; s < splits; s += 64) sv += ld(rs, (unsigned)(s * M + co) * 4u);
+    sv = wave_sum(sv);
+    if (c == 0) st(make_rsrc(sum_dz, (unsigned)M * 4u), (unsigned)co * 4u, sv);
+  }
+  __shared__ float red[4][36][64];
+  __shared__ float grad[64 * 9];
+  float acc[36];
+#pragma unroll
+  for (int pt = 0; pt < 36; ++pt) acc[pt] = 0.f;
+  const unsigned point = (unsigned)(M * C), slab = 36u * point;
+  const unsigned e0 = (unsigned)(co * C + ci0 + c);
+  for (int s = q; s < splits; s += 4)
+#pragma unroll
+    for (int pt = 0; pt < 36; ++pt) acc[pt] += ld(rp, ((unsigned)s * slab + (unsigned)pt * point + e0) * 4u);
+#pragma unroll
+  for (int pt = 0; pt < 36; ++pt) red[q][pt][c] = acc[pt];
+  __syncthreads();
+  if (q == 0) {
+    float r[3][6];                                         // G^T P, a column of the points at a time
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {
+      float p[6], o[3];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) p[a] = (red[0][a * 6 + b][c] + red[1][a * 6 + b][c]) + (red[2][a * 6 + b][c] + red[3][a * 6 + b][c]);
+      gt3(p[0], p[1], p[2], p[3], p[4], p[5], o);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) r[a][b] = o[a];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      float o[3];
+      gt3(r[a][0], r[a][1], r[a][2], r[a][3], r[a][4], r[a][5], o);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) grad[c * 9 + a * 3 + b] = o[b];
+    }
+  }
+  __syncthreads();
+  const float sc = scale ? ld(make_rsrc(scale, (unsigned)M * 4u), (unsigned)co * 4u) : 1.f;
+  float part = 0.f;
+  for (int e = tx; e < 64 * 9; e += kBlock) {
+    const unsigned off = ((unsigned)(co * C + ci0) * 9u + (unsigned)e) * 4u;
+    if (dot) part += grad[e] * ld(rw, off);
+    st(rd, off, grad[e] * sc);
+  }
+  if (dot) {
+    __shared__ float redd[4];
+    part = wave_sum(part);
+    if (c == 0) redd[q] = part;
+    __syncthreads();
+    if (tx == 0) st(make_rsrc(dot, (unsigned)((C / 64) * M) * 4u), (unsigned)(blockIdx.x * M + co) * 4u, (redd[0] + redd[1]) + (redd[2] + redd[3]));
+  }
+}
+
 }  // namespace wino
 }  // namespace dasac
 
@@ -366,5 +532,67 @@ extern "C" int dasac_winograd_wgrad_finish(const void* workspace, size_t ws_byte
   hipLaunchKernelGGL(wino::wgrad_finish, dim3(C / 64, M), dim3(wino::kBlock), 0, as_stream(stream), P, P + p_elems, splits, M, C, w, scale,
                      dw, dot, sum_dz, (unsigned)(p_elems * 4), (unsigned)((int64_t)M * C * 9 * 4));
   DASAC_CHECK_LAUNCH("winograd wgrad_finish");
+  return DASAC_OK;
+}
+
+// ---- F(4x4,3x3) weight gradient: entry points -------------------------------------------------------------------------------
+static int wino_geom4(Geom& g, const char* who, int Nb, int C, int H, int W, int dilation) {
+  DASAC_REQUIRE(Nb > 0 && C > 0 && C <= 65535 && H > 0 && W > 0 && dilation > 0, "%s: bad geometry", who);
+  DASAC_REQUIRE((int64_t)Nb * H * W < (1ll << 30), "%s: more than 2^30 pixels", who);
+  g = wino::make_geom<4>(Nb, H, W, dilation);
+  DASAC_REQUIRE(36 * (int64_t)C * g.T * 4 <= wino::kMaxBytes && (int64_t)C * Nb * H * W * 4 <= wino::kMaxBytes,
+                "%s: a tensor exceeds the 4 GiB buffer-descriptor window", who);
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd4_tiles(int Nb, int H, int W, int dilation) {
+  if (Nb <= 0 || H <= 0 || W <= 0 || dilation <= 0) return 0;
+  const int64_t t = (int64_t)Nb * wino::make_axis<4>(H, dilation).tiles * wino::make_axis<4>(W, dilation).tiles;
+  return t < (1ll << 30) ? (int)((t + 3) / 4 * 4) : 0;
+}
+
+extern "C" int dasac_winograd4_input(const float* x, int Nb, int C, int H, int W, int dilation, float* v, size_t v_bytes,
+                                     dasac_stream_t stream) {
+  DASAC_REQUIRE(x && v, "winograd4_input: null pointer");
+  Geom g;
+  const int rc = wino_geom4(g, "winograd4_input", Nb, C, H, W, dilation);
+  if (rc) return rc;
+  const size_t need = (size_t)36 * C * g.T * 4;
+  if (v_bytes < need) return fail(DASAC_EWORKSPACE, "winograd4_input: workspace too small (%zu < %zu)", v_bytes, need);
+  hipLaunchKernelGGL(wino::input_transform4, dim3((g.T + wino::kBlock - 1) / wino::kBlock, C), dim3(wino::kBlock), 0, as_stream(stream), x,
+                     v, g, C, (unsigned)((int64_t)Nb * C * H * W * 4), (unsigned)need);
+  DASAC_CHECK_LAUNCH("winograd input_transform4");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd4_grad_input(const float* dz, int Nb, int M, int H, int W, int dilation, float* dm, size_t dm_bytes,
+                                          dasac_stream_t stream) {
+  DASAC_REQUIRE(dz && dm, "winograd4_grad_input: null pointer");
+  Geom g;
+  const int rc = wino_geom4(g, "winograd4_grad_input", Nb, M, H, W, dilation);
+  if (rc) return rc;
+  const size_t need = (size_t)36 * M * g.T * 4;
+  if (dm_bytes < need) return fail(DASAC_EWORKSPACE, "winograd4_grad_input: workspace too small (%zu < %zu)", dm_bytes, need);
+  hipLaunchKernelGGL(wino::grad_transform4, dim3((g.T + wino::kBlock - 1) / wino::kBlock, M), dim3(wino::kBlock), 0, as_stream(stream), dz,
+                     dm, g, M, (unsigned)((int64_t)Nb * M * H * W * 4), (unsigned)need);
+  DASAC_CHECK_LAUNCH("winograd grad_transform4");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd4_wgrad_finish(const void* workspace, size_t ws_bytes, int M, int C, int T, const float* w,
+                                            const float* scale, float* dw, float* dot, float* sum_dz, dasac_stream_t stream) {
+  DASAC_REQUIRE(workspace && w && dw, "winograd4_wgrad_finish: null pointer");
+  DASAC_REQUIRE(M > 0 && M <= 65535 && C > 0 && C % 64 == 0, "winograd4_wgrad_finish: needs 1..65535 output channels and a multiple of 64 input channels");
+  const int splits = dasac_conv_wgrad_batched_splits(36, M, C, T);
+  DASAC_REQUIRE(splits > 0, "winograd4_wgrad_finish: the batched weight-gradient launch does not take this shape");
+  const size_t need = dasac_conv_wgrad_batched_workspace(36, M, C, T);
+  if (ws_bytes < need) return fail(DASAC_EWORKSPACE, "winograd4_wgrad_finish: workspace too small (%zu < %zu)", ws_bytes, need);
+  const int64_t p_elems = (int64_t)splits * 36 * M * C;
+  DASAC_REQUIRE(p_elems * 4 <= wino::kMaxBytes && (int64_t)M * C * 9 * 4 <= wino::kMaxBytes,
+                "winograd4_wgrad_finish: a tensor exceeds the 4 GiB buffer-descriptor window");
+  const float* P = reinterpret_cast<const float*>(workspace);
+  hipLaunchKernelGGL(wino::wgrad_finish4, dim3(C / 64, M), dim3(wino::kBlock), 0, as_stream(stream), P, P + p_elems, splits, M, C, w, scale,
+                     dw, dot, sum_dz, (unsigned)(p_elems * 4), (unsigned)((int64_t)M * C * 9 * 4));
+  DASAC_CHECK_LAUNCH("winograd wgrad_finish4");
   return DASAC_OK;
 }

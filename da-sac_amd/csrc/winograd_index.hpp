@@ -1,5 +1,5 @@
-// Index arithmetic of the Winograd F(2x2,3x3) path for dilated 3x3 convolutions (winograd.hip): phase sizes, the numbering of
-// tiles, patch and tensor offsets.  Plain integer functions, compiled for the host AND the device: the kernels call exactly what
+// Index arithmetic of the Winograd F(2x2,3x3) and F(4x4,3x3) paths for dilated 3x3 convolutions (winograd.hip): phase sizes, the
+// numbering of tiles, patch and tensor offsets.  Plain integer functions, compiled for the host AND the device: the kernels call exactly what
 // the stand-alone host check (tools/winograd_index_check.cpp) walks, so an offset the check has seen in range is the offset the
 // kernel forms.
 //
@@ -12,6 +12,11 @@
 // Tiles of an axis are numbered g = t*d + p while every phase still has a tile t ("full" part), then the r leftover tiles t = b of
 // the longer phases.  Consecutive g therefore means consecutive pixels: a wave whose lanes run along g reads and writes runs of d
 // adjacent floats, and the four taps of a patch row fill each other's gaps.
+//
+// Everything above is F(2,3) per axis.  The functions that depend on the outputs per tile take them as a template parameter TM
+// (2 by default: F(2x2,3x3); 4: the F(4x4,3x3) weight gradient): a phase of q samples has ceil(q / TM) tiles, tile (p, t) produces
+// the outputs o0 + e*d, e = 0 .. TM-1, o0 = p + TM*d*t, from the TM + 2 inputs o0 + (k - 1)*d, and the longer phases have a
+// leftover tile when q % TM == 0.  The structs are the same for both, so a kernel of either form takes a Geom by value.
 #pragma once
 #include <stdint.h>
 
@@ -46,20 +51,22 @@ DASAC_HD int div(int n, Div f) {
 struct Axis {
   int n, d;      // extent, dilation
   int q, r;      // n = q*d + r
-  int b;         // tiles of a phase with q samples: ceil(q / 2)
+  int b;         // tiles of a phase with q samples: ceil(q / TM)
   int full;      // tiles numbered t*d + p (t < b); 0 when q == 0
-  int tiles;     // full + the leftover tiles (t == b) of the r longer phases, which exist when q is even
+  int tiles;     // full + the leftover tiles (t == b) of the r longer phases, which exist when q % TM == 0
   Div by_d;
 };
+template <int TM = 2>
 DASAC_HD Axis make_axis(int n, int d) {
+  static_assert(TM == 2 || TM == 4, "outputs per tile and axis: 2 or 4 (coord_to_tile shifts by log2)");
   Axis a;
   a.n = n;
   a.d = d;
   a.q = n / d;
   a.r = n - a.q * d;
-  a.b = (a.q + 1) / 2;
+  a.b = (a.q + TM - 1) / TM;
   a.full = a.b * d;
-  a.tiles = a.full + ((a.q & 1) == 0 ? a.r : 0);
+  a.tiles = a.full + ((a.q & (TM - 1)) == 0 ? a.r : 0);
   a.by_d = make_div(d);
   return a;
 }
@@ -75,69 +82,76 @@ DASAC_HD void tile_decode(const Axis& a, int g, int& p, int& t) {
   }
 }
 DASAC_HD int tile_encode(const Axis& a, int p, int t) { return t < a.b ? t * a.d + p : a.full + p; }
-// first output coordinate of a tile; the patch's inputs are first_out + (k - 1)*d, k = 0..3, its outputs first_out + e*d, e = 0..1
-DASAC_HD int first_out(const Axis& a, int p, int t) { return p + 2 * a.d * t; }
-// output coordinate -> (tile number, e = which of the tile's two outputs)
+// first output coordinate of a tile; the patch's inputs are first_out + (k - 1)*d, k = 0..TM+1, its outputs first_out + e*d, e = 0..TM-1
+template <int TM = 2>
+DASAC_HD int first_out(const Axis& a, int p, int t) { return p + TM * a.d * t; }
+// output coordinate -> (tile number, e = which of the tile's TM outputs): the phase's sample index i splits into (i / TM, i % TM)
+template <int TM = 2>
 DASAC_HD void coord_to_tile(const Axis& a, int o, int& g, int& e) {
   const int i = div(o, a.by_d), p = o - i * a.d;
-  e = i & 1;
-  g = tile_encode(a, p, i >> 1);
+  e = i & (TM - 1);
+  g = tile_encode(a, p, i >> (TM == 4 ? 2 : 1));
 }
 
 struct Geom {
   Axis ay, ax;
   int N, H, W, HW;
   int tiles_img;          // ay.tiles * ax.tiles
-  int T;                  // N * tiles_img: the pixel axis of the 16 point GEMMs
+  int T;                  // the pixel axis of the point GEMMs.  TM == 2: N * tiles_img.  TM == 4: that rounded up to a multiple of 4
+                          // (the batched point contraction needs it); tiles N * tiles_img .. T-1 are padding, zero at every point
   Div by_tiles_img, by_tx, by_hw, by_w;
 };
+template <int TM = 2>
 DASAC_HD Geom make_geom(int N, int H, int W, int d) {
   Geom g;
-  g.ay = make_axis(H, d);
-  g.ax = make_axis(W, d);
+  g.ay = make_axis<TM>(H, d);
+  g.ax = make_axis<TM>(W, d);
   g.N = N;
   g.H = H;
   g.W = W;
   g.HW = H * W;
   g.tiles_img = g.ay.tiles * g.ax.tiles;
-  g.T = N * g.tiles_img;
+  g.T = TM == 4 ? (N * g.tiles_img + 3) / 4 * 4 : N * g.tiles_img;
   g.by_tiles_img = make_div(g.tiles_img);
   g.by_tx = make_div(g.ax.tiles);
   g.by_hw = make_div(g.HW);
   g.by_w = make_div(W);
   return g;
 }
-// tile -> (image, first output row, first output column)
+// tile -> (image, first output row, first output column); not for the padding tiles of TM == 4 (real_tile)
+template <int TM = 2>
 DASAC_HD void tile_origin(const Geom& g, int tile, int& n, int& y0, int& x0) {
   n = div(tile, g.by_tiles_img);
   const int rem = tile - n * g.tiles_img;
   const int gy = div(rem, g.by_tx), gx = rem - gy * g.ax.tiles;
   int p, t;
   tile_decode(g.ay, gy, p, t);
-  y0 = first_out(g.ay, p, t);
+  y0 = first_out<TM>(g.ay, p, t);
   tile_decode(g.ax, gx, p, t);
-  x0 = first_out(g.ax, p, t);
+  x0 = first_out<TM>(g.ax, p, t);
 }
-// flattened output pixel (n, y, x) -> its tile and position (ey, ex) inside the tile's 2x2 outputs; `rem` = y*W + x
+DASAC_HD bool real_tile(const Geom& g, int tile) { return tile < g.N * g.tiles_img; }
+// flattened output pixel (n, y, x) -> its tile and position (ey, ex) inside the tile's TM x TM outputs; `rem` = y*W + x
+template <int TM = 2>
 DASAC_HD void pixel_tile(const Geom& g, int pix, int& n, int& rem, int& tile, int& ey, int& ex) {
   n = div(pix, g.by_hw);
   rem = pix - n * g.HW;
   const int y = div(rem, g.by_w), x = rem - y * g.W;
   int gy, gx;
-  coord_to_tile(g.ay, y, gy, ey);
-  coord_to_tile(g.ax, x, gx, ex);
+  coord_to_tile<TM>(g.ay, y, gy, ey);
+  coord_to_tile<TM>(g.ax, x, gx, ex);
   tile = (n * g.ay.tiles + gy) * g.ax.tiles + gx;
 }
 
 constexpr unsigned kOutside = 0xFFFFFFFFu;   // byte offset of a tap outside the image: past any buffer extent, reads as zero
 
-// byte offset into x [N, C, H, W] of tap (ky, kx) of the patch whose first output is (y0, x0); kOutside for the zero padding
+// byte offset into x [N, C, H, W] of tap (ky, kx), 0 .. TM+1 each, of the patch whose first output is (y0, x0); kOutside for the zero padding
 DASAC_HD unsigned patch_offset(const Geom& g, int C, int n, int c, int y0, int x0, int ky, int kx) {
   const int y = y0 + (ky - 1) * g.ay.d, x = x0 + (kx - 1) * g.ax.d;
   if ((unsigned)y >= (unsigned)g.H || (unsigned)x >= (unsigned)g.W) return kOutside;
   return (unsigned)((n * C + c) * g.HW + y * g.W + x) * 4u;
 }
-// byte offset into a transformed tensor [16][C][T] (V, or the point GEMMs' output)
+// byte offset into a transformed tensor [points][C][T] (V, dM, or the point GEMMs' output), pt < 16 or 36: (TM + 2)^2 points
 DASAC_HD unsigned point_offset(const Geom& g, int C, int pt, int c, int tile) { return (unsigned)((pt * C + c) * g.T + tile) * 4u; }
 // byte offset into an NCHW activation of M channels
 DASAC_HD unsigned out_offset(const Geom& g, int M, int n, int m, int rem) { return (unsigned)((n * M + m) * g.HW + rem) * 4u; }

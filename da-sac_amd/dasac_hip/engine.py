@@ -184,7 +184,11 @@ class ConvOp:
                 dot = bp.dot_slice(spec, dz.device)
             if want_bn or want_bias:      # channel sums ride along with the wgrad kernel
                 sums = bp.sums_dest(b_idx, want_bias and bias_is_sums, spec.cout, dz.device)
-            if ops.winograd_wgrad_routed(spec, xin.shape[0], xin.shape[2], xin.shape[3]):
+            if ops.winograd4_wgrad_routed(spec, xin.shape[0], xin.shape[2], xin.shape[3]):
+                # the same layers on maps of at least two whole 4x4-output tiles per phase: F(4x4,3x3), 1.71 x fewer multiplies again
+                bp.store(w_idx, [ops.winograd4_wgrad(spec, dz, xin, self.convs[0].weight.detach(), scale=scale, dot=dot, sum_dz=sums,
+                                                     out=bp.dest(w_idx[0]))])
+            elif ops.winograd_wgrad_routed(spec, xin.shape[0], xin.shape[2], xin.shape[3]):
                 # wide dilated 3x3 (conv2 of layer3 and layer4): the adjoint of the forward's F(2x2,3x3) form, 2.25 x fewer multiplies
                 bp.store(w_idx, [ops.winograd_wgrad(spec, dz, xin, self.convs[0].weight.detach(), scale=scale, dot=dot, sum_dz=sums,
                                                     out=bp.dest(w_idx[0]))])

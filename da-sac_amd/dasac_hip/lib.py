@@ -95,6 +95,10 @@ PROTOTYPES = {
     "dasac_conv_wgrad_batched_workspace": (_sz, [_i, _i, _i, _i]),
     "dasac_conv_wgrad_batched": (_i, [_p, _p, _i, _i, _i, _i, _l, _l, _i, _p, _sz, _p]),
     "dasac_winograd_wgrad_finish": (_i, [_p, _sz, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "dasac_winograd4_tiles": (_i, [_i, _i, _i, _i]),
+    "dasac_winograd4_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "dasac_winograd4_grad_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "dasac_winograd4_wgrad_finish": (_i, [_p, _sz, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "dasac_conv_pack_expanded":(_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dasac_tap_gather": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "dasac_tap_scatter": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),

@@ -319,7 +319,8 @@ def conv_dgrad(spec, dz, weights, in_hw, scale=None, res=None, mask=None, table=
 # ----------------------------------------------------------------------------------------------
 # Algorithm of the forward / data-gradient / weight-gradient GEMMs of an eligible convolution:
 #   "auto"    Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2) and, for the weight gradient,
-#             where `winograd_wgrad_routed` does (layer4's and layer3's conv2), direct elsewhere;
+#             where `winograd4_wgrad_routed` (F(4x4,3x3): the same layers on large maps) or `winograd_wgrad_routed` does (layer4's
+#             and layer3's conv2), direct elsewhere;
 #   "direct"  the direct implicit GEMM everywhere.
 ALGORITHM = "auto"
 # Layer3's 256 -> 256 measures faster through the batched Winograd path too (0.69 -> 0.59 ms per conv, 11.6 ms per cfg-3 step) but stays
@@ -481,6 +482,65 @@ def winograd_wgrad(spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=N
     with PROFILE.span("winograd_wgrad_finish", 0.0, None, float(slab_bytes) + 8.0 * weight.numel()):
         L.check(lib.dasac_winograd_wgrad_finish(slabs.data_ptr(), slabs.numel(), M, C, T, _c(weight).data_ptr(), L.ptr(scale), dw.data_ptr(),
                                                 L.ptr(dot), L.ptr(sum_dz), L.stream_ptr()), "dasac_winograd_wgrad_finish")
+    return dw
+
+
+# The same weight gradient as F(4x4,3x3) (evaluation points 0, 1, -1, 2, -1/2, inf): 36 point products per 4x4-output tile against
+# 4 x 16, and transformed tensors of 0.59 times the size, at a few times the rounding error -- which a weight gradient, a terminal
+# sum, can take and the forward and the data gradient (ReLU patterns, pseudo-label thresholds) cannot.  Routed per layer where it
+# measured faster than the F(2x2) form on its own (profiles/winograd4_wgrad_ab.txt): a (Cin, Cout) pair missing here stays F(2x2).
+WINOGRAD4_WGRAD_LAYERS = {(256, 256), (512, 512)}
+WINOGRAD4_MIN_SAMPLES = 8                    # per phase and axis: two whole four-output tiles; below that most of a tile is overhang
+
+
+def winograd4_wgrad_routed(spec, Nb, H, W):
+    """The engine's rule for the F(4x4,3x3) weight gradient, consulted before `winograd_wgrad_routed`: that rule's conditions
+    (eligible, fp32, wide enough, inside the 4 GiB window, channel counts multiples of 128) and on both axes n // d >= 8."""
+    if ALGORITHM != "auto" or not winograd_ok(spec) or spec.cin * spec.cout < WINOGRAD_WGRAD_MIN_CHANNEL_PRODUCT:
+        return False
+    if spec.cin % 128 or spec.cout % 128 or (spec.cin, spec.cout) not in WINOGRAD4_WGRAD_LAYERS:
+        return False
+    d = spec.branches[0][2]
+    if H // d < WINOGRAD4_MIN_SAMPLES or W // d < WINOGRAD4_MIN_SAMPLES:
+        return False
+    lib = L.load()
+    T = lib.dasac_winograd4_tiles(Nb, H, W, d)
+    return T > 0 and 144 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES \
+        and lib.dasac_conv_wgrad_batched_splits(36, spec.cout, spec.cin, T) > 0
+
+
+def winograd4_wgrad(spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=None):
+    """`winograd_wgrad` in the F(4x4,3x3) form: the 6x6-patch input transform of x, A dY A^T of every tile's 4x4 output pixels,
+    ONE batched launch of the 36 point contractions, and the finish (splits added in a fixed order, G^T (.) G from 6x6 to 3x3,
+    scale[co], `dot` and `sum_dz` as `conv_wgrad` leaves them).  The tile count is padded to a multiple of 4 with zero tiles, so
+    any batch and map size is taken."""
+    lib = L.load()
+    L.require_gpu(dz, x, weight, scale, dot, sum_dz)
+    Nb, C, H, W = x.shape
+    M, d = dz.shape[1], int(spec.branches[0][2])
+    assert winograd_ok(spec) and (C, M) == (spec.cin, spec.cout) and tuple(dz.shape) == (Nb, M, H, W) and x.is_contiguous()
+    assert dot is None or (tuple(dot.shape) == (dot_rows(spec), M) and dot.is_contiguous())
+    T = lib.dasac_winograd4_tiles(Nb, H, W, d)
+    slab_bytes = lib.dasac_conv_wgrad_batched_workspace(36, M, C, T) if T > 0 else 0
+    if slab_bytes == 0 or 144 * max(C, M) * T > _MAX_TENSOR_BYTES:
+        raise L.DasacError("winograd4_wgrad: {} x {} channels over {} tiles has no batched point contraction".format(M, C, T))
+    v_elems, m_elems = 36 * C * T, 36 * M * T
+    ws = L.workspace(4 * (v_elems + m_elems) + slab_bytes, x.device)
+    v, dm, slabs = ws[:4 * v_elems], ws[4 * v_elems:4 * (v_elems + m_elems)], ws[4 * (v_elems + m_elems):]
+    dz = _c(dz)
+    with PROFILE.span("winograd4_wgrad_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
+        L.check(lib.dasac_winograd4_input(x.data_ptr(), Nb, C, H, W, d, v.data_ptr(), v.numel(), L.stream_ptr()), "dasac_winograd4_input")
+    with PROFILE.span("winograd4_wgrad_grad", 0.0, None, 4.0 * (dz.numel() + m_elems)):
+        L.check(lib.dasac_winograd4_grad_input(dz.data_ptr(), Nb, M, H, W, d, dm.data_ptr(), dm.numel(), L.stream_ptr()),
+                "dasac_winograd4_grad_input")
+    with PROFILE.span("winograd4_wgrad_gemm", 2.0 * 36 * M * C * T, (M, C, T, 1, 1, False, False), 4.0 * (v_elems + m_elems + 36 * M * C)):
+        # entry 7 = point (1,1), evaluation point 1 on both axes: its row sums are the channel sums of dz
+        L.check(lib.dasac_conv_wgrad_batched(dm.data_ptr(), v.data_ptr(), 36, M, C, T, M * T, C * T, 7, slabs.data_ptr(), slabs.numel(),
+                                             L.stream_ptr()), "dasac_conv_wgrad_batched")
+    dw = _dest(out, weight)
+    with PROFILE.span("winograd4_wgrad_finish", 0.0, None, float(slab_bytes) + 8.0 * weight.numel()):
+        L.check(lib.dasac_winograd4_wgrad_finish(slabs.data_ptr(), slabs.numel(), M, C, T, _c(weight).data_ptr(), L.ptr(scale), dw.data_ptr(),
+                                                 L.ptr(dot), L.ptr(sum_dz), L.stream_ptr()), "dasac_winograd4_wgrad_finish")
     return dw
 
 

@@ -253,6 +253,24 @@ int dasac_conv_wgrad_batched(const float* a, const float* b, int batch, int M, i
                              int sum_entry, void* workspace, size_t ws_bytes, dasac_stream_t stream);
 int dasac_winograd_wgrad_finish(const void* workspace, size_t ws_bytes, int M, int C, int T, const float* w, const float* scale,
                                 float* dw, float* dot, float* sum_dz, dasac_stream_t stream);
+/* The same weight gradient as Winograd F(4x4,3x3), evaluation points 0, 1, -1, 2, -1/2, inf: 36 point products per 4x4-output tile,
+ * 1.71 x fewer multiplies than the F(2x2) form on large maps, at a few times its rounding error (a weight gradient is a terminal
+ * sum; the forward and the data gradient have no such form here).  The phases are cut into 4x4-output tiles, and
+ * T = dasac_winograd4_tiles(Nb, H, W, dilation) is their count ROUNDED UP to a multiple of 4 (what dasac_conv_wgrad_batched needs);
+ * both transforms write the padding tiles as zeros at all 36 points.
+ *   dasac_winograd4_input        v [36][C][T] = B^T d B of every tile's 6x6 patch of x.  v_bytes >= 36*C*T*4.
+ *   dasac_winograd4_grad_input   dm [36][M][T] = A dY A^T of every tile's 4x4 output pixels of dz.  dm_bytes >= 36*M*T*4.
+ *   dasac_conv_wgrad_batched     batch = 36, strides M*T and C*T, sum_entry = 7: point (1,1), evaluation point 1 on both axes, is
+ *                                the tile's pixel sum.
+ *   dasac_winograd4_wgrad_finish as dasac_winograd_wgrad_finish over the 36 slabs per split
+ *                                (ws_bytes >= dasac_conv_wgrad_batched_workspace(36, M, C, T)), G^T (.) G from 6x6 to 3x3. */
+int dasac_winograd4_tiles(int Nb, int H, int W, int dilation);
+int dasac_winograd4_input(const float* x, int Nb, int C, int H, int W, int dilation, float* v, size_t v_bytes,
+                          dasac_stream_t stream);
+int dasac_winograd4_grad_input(const float* dz, int Nb, int M, int H, int W, int dilation, float* dm, size_t dm_bytes,
+                               dasac_stream_t stream);
+int dasac_winograd4_wgrad_finish(const void* workspace, size_t ws_bytes, int M, int C, int T, const float* w, const float* scale,
+                                 float* dw, float* dot, float* sum_dz, dasac_stream_t stream);
 
 /* Tap-expanded evaluation of few-output-channel, many-tap convolutions -- the ASPP classifiers
  * (deeplabv2.py:101-116): Y[(tap,co)] = 1x1 GEMM over taps*Cp channels (dasac_conv_gemm with weights

@@ -7,7 +7,8 @@ recorded bits) and weight gradient (scaled, with the frozen BN's dot rows and ch
 Per repetition: `iters` back-to-back evaluations between one HIP event pair -> ms per conv, summing every launch that replaces
 the direct one (input transform + the 16 point GEMMs, as one batched launch or as 16 + output transform; weight gradient: both
 transforms + the batched point contraction + finish, against conv_wgrad + its finish).  A second pass splits
-the Winograd time per kernel with an event pair per launch (ops.PROFILE).  With DASAC_LIB naming an older build of the library
+the Winograd time per kernel with an event pair per launch (ops.PROFILE); the weight gradient has a second Winograd leg, F(4x4,3x3)
+(ops.winograd4_wgrad), with its own split.  With DASAC_LIB naming an older build of the library
 the figures are that build's (the A/B against the parent commit on the same box): --direct-only for its direct GEMM,
 --gemm-schedule 2 for the 16-launch form an older build has."""
 import argparse
@@ -80,6 +81,11 @@ def main():
             legs["dgrad   winograd" + sfx] = lambda sched=sched: ops.winograd_conv(dz, u_t, dx, d, mask_bits=mask, gemm_schedule=sched)
         if hasattr(L.load(), "dasac_conv_wgrad_batched"):      # absent from an older build named by DASAC_LIB
             legs["wgrad   winograd"] = lambda: ops.winograd_wgrad(spec, dz, x, w, scale=scale, dot=dot, sum_dz=sums, out=dw)
+        if hasattr(L.load(), "dasac_winograd4_wgrad_finish"):
+            legs["wgrad   winograd F(4x4)"] = lambda: ops.winograd4_wgrad(spec, dz, x, w, scale=scale, dot=dot, sum_dz=sums, out=dw)
+            T4 = L.load().dasac_winograd4_tiles(N, S, S, d)
+            print("F(4x4) weight gradient: {} tiles, {} pixel splits of the 36 point contractions".format(
+                T4, L.load().dasac_conv_wgrad_batched_splits(36, C, C, T4)))
         legs["filter transform (per weight update, forward + dgrad)"] = lambda: (ops.winograd_filter(spec, w, False, scale, out=u_f),
                                                                                  ops.winograd_filter(spec, w, True, scale, out=u_t))
     print("library: {}   shape: {} x {} -> {} x {} x {}, dilation {}   {} iterations per repetition".format(
