@@ -114,6 +114,8 @@ PROTOTYPES = {
     "dasac_view_consistency": (_i, [_p, _i, _i, _i, _l, _f, _p, _p, _p, _p]),
     "dasac_boundary_counts_workspace": (_sz, [_i, _i, _i, _i]),
     "dasac_boundary_counts": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "dasac_crf_meanfield_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "dasac_crf_meanfield": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "dasac_label_hist": (_i, [_p, _i, _l, _p, _p]),
     "dasac_make_views_table_ints": (_i, [_i, _i]),
     "dasac_make_views": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),

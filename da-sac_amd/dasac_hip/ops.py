@@ -680,6 +680,35 @@ def infer_fuse(sources, flips, size, mode="mean", lut=None, want_conf=False, wan
     return labels, conf, probs
 
 
+def crf_meanfield(probs, image, params, lut=None, want_conf=False, want_probs=False):
+    """Mean-field refinement of fused class probabilities by a locally connected CRF over the image (include/dasac_hip.h:
+    dasac_crf_meanfield): probs fp32 [B,C,H,W] as `infer_fuse` writes them, image fp32 [B,Ci,H,W] as the network sees it, `params` a
+    crf.CrfParams (anything with its nine attributes; the library checks the ranges).  One launch per iteration, the last one
+    fusing arg-max, `lut` and confidence.  Returns (labels u8 [B,H,W], conf f32 [B,H,W] or None, probs f32 [B,C,H,W] or None)."""
+    lib = L.load()
+    L.require_gpu(probs, image, lut)
+    if probs.dtype != torch.float32 or probs.dim() != 4 or image.dtype != torch.float32 or image.dim() != 4:
+        raise L.DasacError("crf_meanfield takes float32 probabilities [B,C,H,W] and a float32 image [B,Ci,H,W] (got {} {} and {} {})".format(
+            probs.dtype, tuple(probs.shape), image.dtype, tuple(image.shape)))
+    B, Cn, H, W = probs.shape
+    if image.shape[0] != B or tuple(image.shape[2:]) != (H, W):
+        raise L.DasacError("crf_meanfield: the image must be [{},Ci,{},{}] like the probabilities (got {})".format(B, H, W, tuple(image.shape)))
+    probs, image = _c(probs), _c(image)
+    if lut is not None:
+        assert lut.dtype == torch.uint8 and lut.numel() >= Cn and lut.is_contiguous()
+    n_iter = int(params.n_iter)
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=probs.device)
+    conf = torch.empty((B, H, W), dtype=torch.float32, device=probs.device) if want_conf else None
+    out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=probs.device) if want_probs else None
+    ws = L.workspace(lib.dasac_crf_meanfield_workspace(B, Cn, H, W, n_iter), probs.device)
+    L.check(lib.dasac_crf_meanfield(probs.data_ptr(), image.data_ptr(), B, Cn, image.shape[1], H, W, int(params.radius),
+                                    int(params.dilation), float(params.w_app), float(params.theta_alpha), float(params.theta_beta),
+                                    float(params.w_smooth), float(params.theta_gamma), float(params.compat), n_iter, L.ptr(lut),
+                                    labels.data_ptr(), L.ptr(conf), L.ptr(out), ws.data_ptr(), ws.numel(), L.stream_ptr()),
+            "dasac_crf_meanfield")
+    return labels, conf, out
+
+
 def upsample_bwd(grad_up, low_hw, gscale=None):
     lib = L.load()
     L.require_gpu(grad_up, gscale)

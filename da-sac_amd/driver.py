@@ -463,8 +463,19 @@ def _ms_plan(H, W, scales, flip):
     return plan
 
 
+def crf_refine(probs, image, params, lut=None, want_conf=False, want_probs=False):
+    """Mean-field CRF refinement (crf.CrfParams; include/dasac_hip.h: dasac_crf_meanfield) of class probabilities fp32 [B,C,H,W] --
+    what infer_label_maps_ms(..., want_probs=True) returns -- over the image fp32 [B,Ci,H,W] the network saw.  Returns (labels u8
+    [B,H,W] through `lut` if given, conf f32 [B,H,W] or None, probs f32 [B,C,H,W] or None) of the refined distribution.  One launch
+    per iteration; torch only allocates."""
+    from dasac_hip import ops
+    if lut is not None and not torch.is_tensor(lut):
+        lut = torch.tensor(list(lut), dtype=torch.uint8, device=probs.device)
+    return ops.crf_meanfield(probs, image, params, lut, want_conf, want_probs)
+
+
 def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="mean", lut=None, teacher=False, want_conf=False,
-                        want_probs=False):
+                        want_probs=False, crf=None):
     """infer_label_maps with test-time augmentation: the image at every scale of `scales`, plain and (with `flip`) mirrored, the
     class probabilities of all of them fused by mean or max (`mode`) at the image's own size.  Per scale s the backbone sees
     scaled_size(H, W, s) pixels: ONE ops.image_pyramid launch makes the scaled (and mirrored) input -- none for s == 1.0 without
@@ -472,7 +483,10 @@ def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="me
     over all the halves (the mirrored half is a batch slice of the same logits tensor) writes the uint8 label map.  No
     upsampled, flipped, softmaxed or summed [B,C,H,W] tensor exists; torch only allocates.  At most 8 sources (scales x
     orientations).  Returns (labels u8 [B,H,W], conf f32 [B,H,W] or None, probs f32 [B,C,H,W] or None): conf is the winning fused
-    probability, probs all of them (infer_val.py's D_SAVE_RAW).  `lut`, `teacher` as infer_label_maps."""
+    probability, probs all of them (infer_val.py's D_SAVE_RAW).  `lut`, `teacher` as infer_label_maps.
+    With `crf` (a crf.CrfParams) the fused probabilities go through crf_refine over `image` -- the step DeepLabv2's published
+    pipeline ends in -- and labels, conf and probs are those of the refined distribution; infer_fuse's own label map is discarded.
+    None (the default) leaves the call launch for launch what it is without the argument."""
     from dasac_hip import ops
     B, _, H, W = image.shape
     plan = _ms_plan(H, W, scales, flip)
@@ -486,10 +500,13 @@ def infer_label_maps_ms(net, image, scales=(0.5, 0.75, 1.0), flip=True, mode="me
             if flip:
                 sources.append(logits[B:])
                 flips.append(True)
-        return ops.infer_fuse(sources, flips, (H, W), mode, lut, want_conf, want_probs)
+        if crf is None:
+            return ops.infer_fuse(sources, flips, (H, W), mode, lut, want_conf, want_probs)
+        _, _, probs = ops.infer_fuse(sources, flips, (H, W), mode, None, False, True)
+        return crf_refine(probs, image, crf, lut, want_conf, want_probs)
 
 
-def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confusion=False, boundary_radius=0):
+def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confusion=False, boundary_radius=0, crf=None):
     """mIoU over (image, label) batches: argmax + per-class tp/fp/fn in one kernel pass per batch
     (train.py:339-469, utils/metrics.py:9-53); counts are all-reduced when a process group exists.
     With `scales` (or `flip`) the prediction is infer_label_maps_ms's label map (scales defaults to (1.0,) when only `flip` is
@@ -500,15 +517,17 @@ def validation_iou(net, batches, num_classes=19, scales=None, flip=False, confus
     ground truth, column = prediction, index C = no class; see summarise_confusion).
     With `boundary_radius` R > 0 one ops.boundary_counts per batch runs beside that pass on the same prediction, and the return value
     gains a last element: the boundary table int64 [R+1,5,C] on the host, summed over ranks (summarise_boundary reads
-    {"prediction": table}).  0 changes nothing."""
+    {"prediction": table}).  0 changes nothing.
+    With `crf` (a crf.CrfParams) the prediction is the CRF-refined map of infer_label_maps_ms(..., crf=crf): it implies that path
+    (scales (1.0,) if none is given), and the counters and the boundary table read the refined maps."""
     from dasac_hip import ops
     core = _unwrap(net)
     counts, boundary, radius = None, None, int(boundary_radius)
-    multi_scale = scales is not None or flip
+    multi_scale = scales is not None or flip or crf is not None
     with eval_mode(core), torch.no_grad():
         for image, gt in batches:
             if multi_scale:
-                maps, _, _ = infer_label_maps_ms(net, image, (1.0,) if scales is None else scales, flip)
+                maps, _, _ = infer_label_maps_ms(net, image, (1.0,) if scales is None else scales, flip, crf=crf)
                 if confusion:
                     counts, _ = ops.confusion_counts([], [maps], gt, counts, num_classes=num_classes)
                 else:

@@ -737,6 +737,35 @@ int dasac_boundary_counts(const float* scores0, const float* scores1, const floa
                           const void* labels0, const void* labels1, int labels_u8_mask, const int64_t* gt, int B, int C, int H,
                           int W, int R, int ignore_index, int64_t* table, void* workspace, size_t ws_bytes, dasac_stream_t stream);
 
+/* Mean-field refinement of an inference label map: a locally connected CRF (the ConvCRF form of Teichmann & Cipolla, 2018: truncated
+ * Gaussian kernels on a dilated window, Potts compatibility) over the fused class probabilities and the image -- the step DeepLabv2's
+ * published pipeline ends in; the reference only kept a place for it (infer_val.py:134).
+ *   probs P: fp32 [B,C,H,W], class probabilities as dasac_infer_fuse writes them; image I: fp32 [B,Ci,H,W], the image as the network
+ *   sees it (normalised): theta_beta is in the image's own units.
+ *   unary and start   u_i[c] = log(max(P_i[c], 1e-20)); Q^0 = P as given, not renormalised.
+ *   taps              offsets o = (d a, d b) for a, b in [-r, r], (a, b) != (0, 0), in row-major order of (a, b); a neighbour
+ *                     j = i + o counts only when it lies inside the image.
+ *   kernel weight     k_ij = w_app exp(-|o|^2 / (2 theta_alpha^2) - sum_ch (I_i - I_j)^2 / (2 theta_beta^2))
+ *                            + w_smooth exp(-|o|^2 / (2 theta_gamma^2)), |o| in pixels.
+ *   message           den_i = sum_j k_ij; m_i[c] = sum_j k_ij Q^(t-1)_j[c] / den_i when den_i > 0, else 0: a convex combination, so
+ *                     border pixels and 1 x 1 images need no special case.
+ *   update            Q^t_i = softmax_c(u_i[c] + compat m_i[c]), all pixels in parallel from Q^(t-1).
+ *   after n_iter updates: labels uint8 [B,H,W] = lut[argmax_c Q] (lut: uint8, at least C entries) or the arg-max itself when lut is
+ *   NULL, first maximum wins; conf (optional) fp32 [B,H,W], the winning Q; probs_out (optional) fp32 [B,C,H,W], Q itself.
+ * 1 <= C <= 32, 1 <= Ci <= 4, 1 <= r <= 5, 1 <= d <= 4 with r d <= 8, 1 <= n_iter <= 16; the thetas > 0; w_app, w_smooth >= 0 with a
+ * positive sum; compat >= 0, all finite; B, H, W >= 1, any H and W; every tensor below 4 GiB - 4 KiB.  probs, image and labels are
+ * non-NULL, fp32 pointers aligned to 4 bytes and nothing more; outputs and workspace overlap neither the inputs nor each other.  The
+ * workspace is aligned to 16 bytes and holds dasac_crf_meanfield_workspace(B, C, H, W, n_iter) bytes: the Q buffers the iterations
+ * alternate between (one for n_iter == 1, else two); less is DASAC_EWORKSPACE, anything else above DASAC_EINVAL, both before any
+ * launch.  One launch per iteration on `stream`, the last one fusing arg-max, LUT and confidence; the taps are summed in their order
+ * by one thread per pixel, no atomics: the same bits on every run and wherever the tensors lie.  No load or store leaves a tensor;
+ * no allocation, no synchronisation. */
+size_t dasac_crf_meanfield_workspace(int B, int C, int H, int W, int n_iter);
+int dasac_crf_meanfield(const float* probs, const float* image, int B, int C, int Ci, int H, int W, int radius, int dilation,
+                        float w_app, float theta_alpha, float theta_beta, float w_smooth, float theta_gamma, float compat, int n_iter,
+                        const uint8_t* lut, uint8_t* labels, float* conf, float* probs_out, void* workspace, size_t ws_bytes,
+                        dasac_stream_t stream);
+
 /* Per-image class statistics for importance-sampled target selection (tools/compute_IS_weights.py:58-83, on the device):
  * counts[b][v] += number of pixels of image b with value v, v in 0..255 (value 255 is counted too; callers drop it).
  * labels: [B][HW] uint8, any alignment (an unaligned head and a tail of any length per image are read byte by byte, the
