@@ -199,10 +199,16 @@ def stats_exact_ok(out, tile=128):
     return True
 
 
-def dot_rows_ref(w, g_unscaled, block=64):
-    """[rows, Cout]: row r = sum over input channels 64 r .. 64 r + 63 and taps of W * G (G: the UNSCALED weight gradient)."""
+def dot_rows_ref(w, g_unscaled, block=64, flat=False):
+    """[rows, Cout]: row r = sum over input channels 64 r .. 64 r + 63 and taps of W * G (G: the UNSCALED weight gradient).
+    flat (layers of fewer than 32 input channels): the rows run along the whole k axis instead, k = tap * Cin + ci; the row count
+    of either form is dasac_conv_wgrad_dot_rows(Cin, taps)."""
     cout, cin = w.shape[:2]
-    prod = (w.double() * g_unscaled.double()).reshape(cout, cin, -1).sum(-1)          # [cout, cin]
+    prod = (w.double() * g_unscaled.double()).reshape(cout, cin, -1)
+    if flat:
+        prod, cin = prod.transpose(1, 2).reshape(cout, -1), prod.shape[1] * prod.shape[2]
+    else:
+        prod = prod.sum(-1)                                                           # [cout, cin]
     rows = (cin + block - 1) // block
     prod = F.pad(prod, (0, rows * block - cin)).view(cout, rows, block).sum(-1)
     return prod.t().contiguous()
@@ -211,7 +217,7 @@ def dot_rows_ref(w, g_unscaled, block=64):
 def dot_exact_ok(w, dz, x, branches, stride):
     """sum |W||G| per 64-channel block below 2^24, with |G| bounded by sum |dz||x|."""
     (ga,) = conv_dw(dz.abs(), x.abs(), [w.abs()], branches, stride)
-    return _below(dot_rows_ref(w.abs(), ga))
+    return _below(dot_rows_ref(w.abs(), ga, flat=w.shape[1] < 32))
 
 
 def bn_param_grads_ref(dot, sum_dz, mean, invstd, scale, conv_bias):
@@ -331,6 +337,63 @@ TAIL_CASE = ("tail", 128, 1024, [(3, 3, 2, 2)], 1, (1, 129, 128))
 PIX_CASES = [("pix_m256", 64, 256, [(1, 1, 1, 0)], 1, (2, 25, 33)), ("pix_m19", 48, 19, [(3, 3, 1, 1)], 1, (3, 19, 23))]
 BATCHED = (3, 16, 136, 129)                                                       # entries, C, M (padded to 256), T (two pixel tiles)
 X3_BATCH = 2
+
+
+# ----------------------------------------------------------------------------------------------
+# the cases of test_gpu_conv_schedules_exact.py: the hand-off schedules and the weight gradient's split plans at the points where
+# their integer rules branch (gemm_schedule_ref.py names what each plan reaches; test_gemm_schedule_cpu.py checks that from the
+# model, test_conv_exact_cpu.py the lattice claims).  Same layout: name, cin, cout, branches, stride, (N, H, W)
+# ----------------------------------------------------------------------------------------------
+_P1, _P3 = [(1, 1, 1, 0)], [(3, 3, 1, 1)]
+STREAMK_CASES = [
+    ("spans", 256, 1024, _P1, 1, (1, 160, 160)),             # 1600 tiles x 16 steps, 33 per range: deposit, whole tiles, then own
+    ("whole_tile_ranges", 256, 1024, _P1, 1, (1, 100, 128)),  # 800 tiles x 16 steps: ranges 512 .. 767 are exactly one tile
+    ("aligned", 1024, 256, _P1, 1, (1, 48, 64)),             # 48 tiles x 64 steps = 768 x 4: no remainder, ranges start on tiles
+    ("many_contributors", 256, 128, _P3, 1, (1, 24, 32)),    # 6 tiles x 144 steps: 143 contributors to one tile
+    ("ragged", 128, 200, _P3, 1, (1, 50, 60)),               # M = 200: two M tiles, rows past M; 3000 pixels: a ragged last tile
+    ("three_m_tiles", 1168, 384, _P1, 1, (1, 25, 40)),       # m_tiles = 3, 73 K-steps
+]
+STREAMK_RESERVED_CASES = STREAMK_CASES[:3] + [SCHEDULE_CASE]  # run at every reserved-CU setting below
+RESERVED = (0, 8, 64, 128)
+# split-K tails, the library's own choice
+TAIL_CASES = [
+    ("split5", 1168, 1024, _P1, 1, (2, 1, 9767)),            # 73 steps in 5 ranges, 200 tail tiles, 19534 pixels: ragged last tile
+    ("m3", 1040, 384, _P1, 1, (5, 121, 73)),                 # m_tiles = 3: 1023 leading tiles, 15 tail tiles, 65 steps in 8 ranges
+    ("m5", 1040, 640, _P1, 1, (1, 160, 172)),                # m_tiles = 5: 1020 leading tiles, 55 tail tiles
+    ("two_rounds", 1024, 1024, _P1, 1, (1, 160, 208)),       # 2048 leading tiles, 32 tail tiles
+    ("reserved8", 1040, 1024, _P1, 1, (1, 128, 140)),        # planned for 248 CUs: 96 tail tiles
+]
+TAIL_RESERVED = {"reserved8": 8}                             # name -> reserved CUs the plan is made for (0 otherwise)
+# weight gradients
+WGRAD_CASES = [
+    ("quad", 128, 128, _P1, 1, (1, 59, 70)),                 # 4130 pixels: 16 splits of 288, one empty, the last one 98 pixels
+    ("qtap", 128, 128, _P3, 1, (1, 59, 70)),                 # the same over 9 k tiles
+    ("k_tile_64", 192, 128, _P1, 1, (1, 59, 70)),            # 64-row k tiles
+    ("strided_fast", 128, 256, _P1, 2, (1, 150, 150)),       # 5625 pixels
+    ("generic", 48, 19, _P3, 1, (1, 70, 75)),                # the 32-row tile: 20 splits, one empty
+    ("bm64", 32, 64, _P3, 1, (1, 70, 75)),                   # the 64-row tile
+    ("splits64", 256, 256, _P1, 1, (1, 128, 129)),           # 16512 pixels: 64 splits, 6 empty (the 1x1 reduce kernel)
+    ("splits64_3x3", 128, 128, _P3, 1, (1, 128, 129)),       # the same plan over 9 k tiles: the tap-walking reduce kernel at 64 splits
+    ("cap_branch", 128, 128, _P1, 1, (1, 448, 448)),         # one tile x 200704 pixels: 768 splits
+    ("cap_branch_stem", 3, 64, [(7, 7, 1, 3)], 2, (1, 897, 897)),   # two tiles x 201601 pixels: 384 splits
+]
+# name -> (x_hi, w_hi) where the long pixel sums need smaller operands than the plain lattice's (3, 2)
+WGRAD_HI = {"cap_branch": (1, 1), "cap_branch_stem": (1, 1), "splits64_3x3": (1, 1)}
+WGRAD_X3_CASES = [c for c in WGRAD_CASES if c[0] in ("quad", "splits64")]
+STREAMK_X3_CASES = [STREAMK_CASES[0], SCHEDULE_CASE]
+
+
+def gemm_shape(case):
+    """(M, Npix, K) of a case's forward GEMM."""
+    name, cin, cout, branches, stride, (N, H, W) = case
+    OH, OW = out_hw(branches, stride, H, W)
+    return cout, N * OH * OW, cin * sum(kh * kw for kh, kw, _, _ in branches)
+
+
+def wgrad_operands(case):
+    name, cin, cout, branches, stride, shape = case
+    x_hi, w_hi = WGRAD_HI.get(name, (3, 2))
+    return plain_operands(cin, cout, branches, stride, shape, x_hi=x_hi, w_hi=w_hi)
 
 
 def case_lists():

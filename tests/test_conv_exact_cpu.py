@@ -8,6 +8,7 @@ import torch
 
 import conv_lattice as cl
 from conv_lattice import BATCHED, PIX_CASES, SCHEDULE_CASE, TAIL_CASE, X3_BATCH, expanded_operands, x3_exact_ok
+from conv_lattice import STREAMK_CASES, STREAMK_X3_CASES, TAIL_CASES, WGRAD_CASES, WGRAD_X3_CASES
 
 _LISTS = cl.case_lists()
 CONV_CASES, DOT_CASES, STATS, WINO_SHAPES, X3_CASES, EXPANDED = (_LISTS[k] for k in ("conv", "dot", "stats", "winograd", "x3", "expanded"))
@@ -140,3 +141,53 @@ def test_expanded_cases(case):
     assert torch.equal(cl.conv_dx(o["dz"], o["ws"], branches, 1, shape[1:], None, F32), cl.f32(dxr))
     for a, b in zip(cl.conv_dw(o["dz"], o["x"], o["ws"], branches, 1, None, F32), cl.conv_dw(o["dz"], o["x"], o["ws"], branches, 1)):
         assert torch.equal(a, cl.f32(b))
+
+
+# ----------------------------------------------------------------------------------------------
+# the cases of test_gpu_conv_schedules_exact.py
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", STREAMK_CASES + TAIL_CASES, ids=[c[0] for c in STREAMK_CASES + TAIL_CASES])
+def test_schedule_lattice_cases(case):
+    """float64 once here: the GPU tests then lean on the fp32 CPU convolution, exact on the lattice."""
+    name, cin, cout, branches, stride, shape = case
+    _check_plain(cin, cout, branches, stride, shape, False, dgrad=False)
+
+
+@pytest.mark.parametrize("case", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
+def test_weight_gradient_split_cases(case):
+    name, cin, cout, branches, stride, shape = case
+    o = cl.wgrad_operands(case)
+    x, w, dz, scale = o["x"], o["ws"][0], o["dz"], o["scale"]
+    assert cl.exact_ok(x, [w], branches, stride, dz, scale, parts=("dw",)) and cl.dot_exact_ok(w, dz, x, branches, stride)
+    (g,) = cl.conv_dw(dz, x, [w], branches, stride)
+    (g32,) = cl.conv_dw(dz, x, [w], branches, stride, None, F32)
+    assert torch.equal(g32, cl.f32(g)) and torch.equal(cl.f32(g * scale.double().view(-1, 1, 1, 1)).double(), g * scale.double().view(-1, 1, 1, 1))
+    rows = cl.dot_rows_ref(w, g, flat=cin < 32)
+    assert rows.shape == ((cin * (w.shape[2] * w.shape[3] if cin < 32 else 1) + 63) // 64, cout) and torch.equal(cl.f32(rows).double(), rows)
+    assert bool((rows.abs().sum(1) > 0).all())
+
+
+@pytest.mark.parametrize("cls", ["A", "B"])
+@pytest.mark.parametrize("case", STREAMK_X3_CASES + WGRAD_X3_CASES, ids=[c[0] for c in STREAMK_X3_CASES + WGRAD_X3_CASES])
+def test_split_bf16_schedule_and_split_cases(case, cls):
+    name, cin, cout, branches, stride, shape = case
+    o = cl.x3_operands(cls, cin, cout, branches, stride, shape)
+    pairs = [(o["fwd"][0], o["fwd"][1])] if case in STREAMK_X3_CASES else [(o["wgrad"][0], [o["wgrad"][1]])]
+    for a, bs in pairs:
+        ha, ta = cl.bf16_split(a)
+        assert np.array_equal(ha.astype(np.float64) + ta, a.numpy())
+        for b in bs:
+            hb, tb = cl.bf16_split(b)
+            assert np.array_equal(hb.astype(np.float64) + tb, b.numpy())
+            assert (not ta.any() or not tb.any()) and (ta.any() or tb.any())             # tail x tail is zero, one cross term is live
+            assert bool(ta.any()) == (cls == "A")
+    if case in STREAMK_X3_CASES:
+        x, ws = o["fwd"]
+        assert cl.exact_ok(x, ws, branches, stride, None, None, o["shift"], o["res_out"], parts=("fwd",))
+        assert torch.equal(cl.conv_fwd(x, ws, branches, stride, None, F32), cl.f32(cl.conv_fwd(x, ws, branches, stride)))
+    else:
+        gz, gx = o["wgrad"]
+        ws = [torch.zeros(cout, cin, kh, kw) for kh, kw, _, _ in branches]
+        assert cl.exact_ok(gx, ws, branches, stride, gz, parts=("dw",))
+        for a, b in zip(cl.conv_dw(gz, gx, ws, branches, stride, None, F32), cl.conv_dw(gz, gx, ws, branches, stride)):
+            assert torch.equal(a, cl.f32(b))
