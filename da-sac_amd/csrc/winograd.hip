@@ -13,6 +13,8 @@
 //   finish             dW[m][c] = scale[m] * G^T (sum_split P) G, the frozen BN's dot rows and sum of dz
 //
 // 2.25 x fewer multiplies than the direct contraction; the price is two passes over [16][C][tiles] tensors.  No new matrix kernel.
+// All three GEMMs also have an F(4x4,3x3) form (36 points per 4x4-output tile, 1.71 x fewer multiplies again; second half of the
+// file): the weight gradient wherever it measured faster, the forward and the data gradient per measured route (ops.WINOGRAD4_ROUTES).
 // Index arithmetic lives in winograd_index.hpp and is walked on the host by tools/winograd_index_check.cpp.  Every global access
 // goes through a buffer descriptor of the tensor's exact extent with the whole offset in the per-lane operand (the scalar
 // offset is not range checked by the hardware): an offset past the extent reads zero / stores nothing.
@@ -260,10 +262,12 @@ __global__ __launch_bounds__(kBlock) void wgrad_finish(const float* __restrict__
 //   B^T = [[2,3,-4,-3,2,0],[0,2,5,1,-2,0],[0,2,1,-5,2,0],[0,-1,-2,1,2,0],[0,-2,1,2,-1,0],[0,2,3,-4,-3,2]]
 //   A   = [[1,0,0,0],[1,1,1,1],[1,-1,1,-1],[1,2,4,8],[1,-1/2,1/4,-1/8],[0,0,0,1]]
 //   G   = [[1/2,0,0],[1/6,1/6,1/6],[1/6,-1/6,1/6],[1/30,1/15,2/15],[16/15,-8/15,4/15],[0,0,1/2]]
-// (tests/winograd4_ref.py holds them as fractions and checks the identities in float64).  Only the weight gradient runs in this form:
-// the forward and the data gradient feed ReLU patterns and stay F(2x2).  The kernels are the twins of the F(2x2) ones above --
-// one thread per (channel, tile), lanes along tiles, exact-extent descriptors -- and additionally write the padding tiles
-// (Geom::T is rounded up to a multiple of 4) as zeros at all 36 points.
+// (tests/winograd4_ref.py holds them as fractions and checks the identities in float64).  The kernels are the twins of the F(2x2)
+// ones above -- one thread per (channel, tile), lanes along tiles, exact-extent descriptors -- and additionally write the padding
+// tiles (Geom::T is rounded up to a multiple of 4) as zeros at all 36 points.  The forward and the data gradient have the same form
+// (filter_transform4 / input_transform4 / 36 point GEMMs / output_transform4, further down): at 2 - 4 x the direct kernel's error
+// against float64, they run where ops.winograd4_routed's table says the end-to-end bounds were measured to hold
+// (profiles/EXPERIMENTS.md).
 __device__ __forceinline__ void bt6(float d0, float d1, float d2, float d3, float d4, float d5, float (&o)[6]) {
   o[0] = (2.f * (d0 + d4) + 3.f * (d1 - d3)) - 4.f * d2;
   o[1] = (2.f * (d1 - d4) + 5.f * d2) + d3;
@@ -417,6 +421,132 @@ __global__ __launch_bounds__(kBlock) void wgrad_finish4(const float* __restrict_
     __syncthreads();
     if (tx == 0) st(make_rsrc(dot, (unsigned)((C / 64) * M) * 4u), (unsigned)(blockIdx.x * M + co) * 4u, (redd[0] + redd[1]) + (redd[2] + redd[3]));
   }
+}
+
+// ---- forward and data gradient as F(4x4,3x3) --------------------------------------------------------------------------------
+// G g along one axis: three taps -> six points
+__device__ __forceinline__ void g6(float g0, float g1, float g2, float (&o)[6]) {
+  constexpr float k6 = 1.f / 6.f, k15 = 1.f / 15.f, k30 = 1.f / 30.f;
+  o[0] = 0.5f * g0;
+  o[1] = k6 * ((g0 + g2) + g1);
+  o[2] = k6 * ((g0 + g2) - g1);
+  o[3] = (k30 * g0 + k15 * g1) + (2.f * k15) * g2;
+  o[4] = ((16.f * k15) * g0 - (8.f * k15) * g1) + (4.f * k15) * g2;
+  o[5] = 0.5f * g2;
+}
+// A^T y along one axis: six points -> four outputs
+__device__ __forceinline__ void at4(float y0, float y1, float y2, float y3, float y4, float y5, float (&o)[4]) {
+  o[0] = (y0 + (y1 + y2)) + (y3 + y4);
+  o[1] = (y1 - y2) + (2.f * y3 - 0.5f * y4);
+  o[2] = (y1 + y2) + (4.f * y3 + 0.25f * y4);
+  o[3] = ((y1 - y2) + y5) + (8.f * y3 - 0.125f * y4);
+}
+
+// The twin of filter_transform: one thread per element (k, m) of the packed [Kpad/4][Mpad][4] matrix, 36 points, U = G g G^T.
+__global__ __launch_bounds__(kBlock) void filter_transform4(const float* __restrict__ Wt, const float* __restrict__ scale,
+                                                             float* __restrict__ U, int Cout, int Cin, int Mpad, int Kpad, int mode,
+                                                             unsigned w_bytes, unsigned u_bytes) {
+  const int idx = blockIdx.x * kBlock + threadIdx.x;      // == offset inside one point's packed matrix
+  const int per_point = Kpad * Mpad;
+  if (idx >= per_point) return;
+  const __amdgpu_buffer_rsrc_t rw = make_rsrc(Wt, w_bytes), ru = make_rsrc(U, u_bytes);
+  const int row4 = Mpad * 4;
+  const int kq = idx / row4, rem = idx - kq * row4;
+  const int m = rem >> 2, k = kq * 4 + (rem & 3);
+  const int M = mode == 0 ? Cout : Cin, K = mode == 0 ? Cin : Cout;
+  const bool real = m < M && k < K;
+  const int co = mode == 0 ? m : k, ci = mode == 0 ? k : m;
+  const float s = (real && scale) ? ld(make_rsrc(scale, (unsigned)Cout * 4u), (unsigned)co * 4u) : 1.f;
+  float t[6][3];                                           // G g, a column of the filter at a time
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    float g[3], o[6];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int tap = mode == 0 ? a * 3 + b : (2 - a) * 3 + (2 - b);
+      g[a] = ld(rw, real ? (unsigned)((co * Cin + ci) * 9 + tap) * 4u : kOutside) * s;
+    }
+    g6(g[0], g[1], g[2], o);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) t[a][b] = o[a];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    float u[6];
+    g6(t[a][0], t[a][1], t[a][2], u);
+#pragma unroll
+    for (int b = 0; b < 6; ++b) st(ru, (unsigned)((a * 6 + b) * per_point + idx) * 4u, u[b]);
+  }
+}
+
+// out = epi(A^T Y A) over Y [36][M][T].  grid (ceil(T / 256), M): one thread per (channel, tile), lanes along tiles, the mapping of
+// input_transform4 and grad_transform4 -- 36 loads for 16 outputs (2.25 per output; one thread per output element would load up to
+// 36 for one), each load a run of 64 consecutive tiles of one point.  Consecutive tile numbers are consecutive phases, so a store
+// instruction writes runs of `d` adjacent floats and the four stores of an output row fill each other's gaps: the mirror of what
+// grad_transform4 reads.  Padding tiles and overhanging outputs store nothing.
+// MASK: the elements whose bit in `mbits` is clear become zero.  The price of the mapping is that a wave no longer holds 64
+// consecutive pixels, so the RECORDED ReLU bits cannot be a ballot here: relu_bits_pack below reads the stored output back.  (Adding
+// the bits into zeroed words with buffer atomics, one per run of outputs that share a word, was built and measured: 0.40 ms for the
+// layer4 launch against 0.12 ms without bits -- the atomics are per lane at the L2; the second pass costs 0.07 ms.)
+template <bool MASK>
+__global__ __launch_bounds__(kBlock) void output_transform4(const float* __restrict__ Y, float* __restrict__ Out, Geom g, int M,
+                                                             const float* __restrict__ shift, int relu,
+                                                             const unsigned* __restrict__ mbits, int w32, unsigned y_bytes,
+                                                             unsigned out_bytes, unsigned bits_bytes) {
+  const int tile = blockIdx.x * kBlock + threadIdx.x;
+  if (!real_tile(g, tile)) return;
+  const int m = blockIdx.y;
+  const __amdgpu_buffer_rsrc_t ry = make_rsrc(Y, y_bytes), ro = make_rsrc(Out, out_bytes);
+  int n, y0, x0;
+  tile_origin<4>(g, tile, n, y0, x0);
+  float t[4][6];                                           // A^T Y, a column of the points at a time
+#pragma unroll
+  for (int b = 0; b < 6; ++b) {
+    float v[6], o[4];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[a] = ld(ry, point_offset(g, M, a * 6 + b, m, tile));
+    at4(v[0], v[1], v[2], v[3], v[4], v[5], o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t[e][b] = o[e];
+  }
+  const float sh = shift ? ld(make_rsrc(shift, (unsigned)M * 4u), (unsigned)m * 4u) : 0.f;
+  const __amdgpu_buffer_rsrc_t rb = make_rsrc(mbits, MASK ? bits_bytes : 0u);
+#pragma unroll
+  for (int ey = 0; ey < 4; ++ey) {
+    float o[4];
+    at4(t[ey][0], t[ey][1], t[ey][2], t[ey][3], t[ey][4], t[ey][5], o);
+    const int y = y0 + ey * g.ay.d;
+#pragma unroll
+    for (int ex = 0; ex < 4; ++ex) {
+      const int x = x0 + ex * g.ax.d;
+      const bool in = y < g.H && x < g.W;
+      const int rem = y * g.W + x, pix = n * g.HW + rem;
+      float v = o[ex];
+      if (shift) v = v + sh;
+      if (relu) v = fmaxf(v, 0.f);
+      if constexpr (MASK) {
+        const unsigned word = __builtin_amdgcn_raw_buffer_load_b32(rb, in ? out_bits_offset(m, w32, pix) : kOutside, 0, 0);
+        v = (word >> (pix & 31)) & 1u ? v : 0.f;
+      }
+      st(ro, in ? out_offset(g, M, n, m, rem) : kOutside, v);
+    }
+  }
+}
+
+// bits[m][pix >> 5] bit (pix & 31) = out[n][m][rem] > 0 over the flattened pixel index pix = n*HW + rem: the ReLU pattern of a stored
+// activation in the layout of the direct epilogue.  grid (ceil(N*H*W / 256), M): one thread per element, lanes along pixels, a wave
+// ballot is two words (the tail of output_transform<1>); every word is written, the bits past the last pixel as zeros.
+__global__ __launch_bounds__(kBlock) void relu_bits_pack(const float* __restrict__ Out, unsigned* __restrict__ obits, Geom g, int M,
+                                                          int w32, unsigned out_bytes, unsigned bits_bytes) {
+  const int pix = blockIdx.x * kBlock + threadIdx.x;
+  const int m = blockIdx.y;
+  const bool live = pix < g.N * g.HW;
+  const int n = live ? div(pix, g.by_hw) : 0;
+  const float v = ld(make_rsrc(Out, out_bytes), live ? out_offset(g, M, n, m, pix - n * g.HW) : kOutside);
+  const unsigned long long ballot = __builtin_amdgcn_ballot_w64(live && v > 0.f);
+  const int lane = threadIdx.x & 63, wcol = pix >> 5;
+  if ((lane & 31) == 0 && wcol < w32)
+    __builtin_amdgcn_raw_buffer_store_b32((unsigned)(lane ? ballot >> 32 : ballot), make_rsrc(obits, bits_bytes), out_bits_offset(m, w32, pix), 0, 0);
 }
 
 }  // namespace wino
@@ -594,5 +724,53 @@ extern "C" int dasac_winograd4_wgrad_finish(const void* workspace, size_t ws_byt
   hipLaunchKernelGGL(wino::wgrad_finish4, dim3(C / 64, M), dim3(wino::kBlock), 0, as_stream(stream), P, P + p_elems, splits, M, C, w, scale,
                      dw, dot, sum_dz, (unsigned)(p_elems * 4), (unsigned)((int64_t)M * C * 9 * 4));
   DASAC_CHECK_LAUNCH("winograd wgrad_finish4");
+  return DASAC_OK;
+}
+
+// ---- F(4x4,3x3) forward and data gradient: entry points ------------------------------------------------------------------------
+extern "C" int dasac_winograd4_filter(const float* w, const float* scale, int Cout, int Cin, int transposed, float* u,
+                                      dasac_stream_t stream) {
+  DASAC_REQUIRE(w && u, "winograd4_filter: null pointer");
+  DASAC_REQUIRE(Cout > 0 && Cin > 0, "winograd4_filter: bad channel counts");
+  const int M = transposed ? Cin : Cout, K = transposed ? Cout : Cin;
+  const int Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K);
+  const int64_t per_point = (int64_t)Kpad * Mpad;
+  DASAC_REQUIRE(36 * per_point * 4 <= wino::kMaxBytes && (int64_t)Cout * Cin * 9 * 4 <= wino::kMaxBytes,
+                "winograd4_filter: operand exceeds the 4 GiB buffer-descriptor window");
+  hipLaunchKernelGGL(wino::filter_transform4, dim3((unsigned)((per_point + wino::kBlock - 1) / wino::kBlock)), dim3(wino::kBlock), 0,
+                     as_stream(stream), w, scale, u, Cout, Cin, Mpad, Kpad, transposed ? 1 : 0, (unsigned)((int64_t)Cout * Cin * 9 * 4),
+                     (unsigned)(36 * per_point * 4));
+  DASAC_CHECK_LAUNCH("winograd filter_transform4");
+  return DASAC_OK;
+}
+
+extern "C" int dasac_winograd4_output(const float* y, size_t y_bytes, int Nb, int M, int H, int W, int dilation, const float* shift,
+                                      int relu, const uint32_t* mask_bits, uint32_t* relu_bits_out, float* out,
+                                      dasac_stream_t stream) {
+  DASAC_REQUIRE(y && out, "winograd4_output: null pointer");
+  DASAC_REQUIRE(!(mask_bits && relu_bits_out), "winograd4_output: record the ReLU pattern OR mask with one");
+  DASAC_REQUIRE(!relu_bits_out || relu, "winograd4_output: relu_bits_out records the pattern of a ReLU epilogue");
+  Geom g;
+  const int rc = wino_geom4(g, "winograd4_output", Nb, M, H, W, dilation);
+  if (rc) return rc;
+  const size_t need = (size_t)36 * M * g.T * 4;
+  if (y_bytes < need) return fail(DASAC_EWORKSPACE, "winograd4_output: workspace too small (%zu < %zu)", y_bytes, need);
+  const int npix = Nb * H * W, w32 = (npix + 31) / 32;
+  DASAC_REQUIRE((int64_t)M * w32 * 4 < (1ll << 31), "winograd4_output: bit mask exceeds 2 GiB");
+  const unsigned bits_bytes = (unsigned)((int64_t)M * w32 * 4), out_bytes = (unsigned)((int64_t)Nb * M * H * W * 4);
+  const dim3 grid((g.T + wino::kBlock - 1) / wino::kBlock, M), block(wino::kBlock);
+  hipStream_t s = as_stream(stream);
+  if (mask_bits)
+    hipLaunchKernelGGL(wino::output_transform4<true>, grid, block, 0, s, y, out, g, M, shift, relu, mask_bits, w32, (unsigned)need, out_bytes,
+                       bits_bytes);
+  else
+    hipLaunchKernelGGL(wino::output_transform4<false>, grid, block, 0, s, y, out, g, M, shift, relu, mask_bits, w32, (unsigned)need, out_bytes,
+                       bits_bytes);
+  if (relu_bits_out) {
+    DASAC_CHECK_LAUNCH("winograd output_transform4");
+    hipLaunchKernelGGL(wino::relu_bits_pack, dim3((npix + wino::kBlock - 1) / wino::kBlock, M), block, 0, s, out, relu_bits_out, g, M, w32,
+                       out_bytes, bits_bytes);
+  }
+  DASAC_CHECK_LAUNCH("winograd output_transform4");
   return DASAC_OK;
 }

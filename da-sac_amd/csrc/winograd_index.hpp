@@ -155,6 +155,8 @@ DASAC_HD unsigned patch_offset(const Geom& g, int C, int n, int c, int y0, int x
 DASAC_HD unsigned point_offset(const Geom& g, int C, int pt, int c, int tile) { return (unsigned)((pt * C + c) * g.T + tile) * 4u; }
 // byte offset into an NCHW activation of M channels
 DASAC_HD unsigned out_offset(const Geom& g, int M, int n, int m, int rem) { return (unsigned)((n * M + m) * g.HW + rem) * 4u; }
+// byte offset into the ReLU bit masks [M][w32] of the word that holds flattened pixel `pix` of channel m
+DASAC_HD unsigned out_bits_offset(int m, int w32, int pix) { return (unsigned)(m * w32 + (pix >> 5)) * 4u; }
 // largest tensor the 32-bit byte offsets reach (kMaxTensorBytes of conv_common.hpp)
 constexpr int64_t kMaxBytes = (1ll << 32) - 4096;
 

@@ -109,6 +109,10 @@ class ConvOp:
         if keep and self.relu and eng._bits_wanted[self.dst] and ops.bits_ok(spec.cout, spec.cin):
             bits = ops.ReluBits(Nb, spec.cout, OH, OW, xin.device)
             saved["bits"][self.dst] = bits
+        if res is None and ops.winograd4_routed(spec, False, Nb, H, W, keep):
+            # a route of ops.WINOGRAD4_ROUTES (no-grad passes of layer4's and layer3's conv2) on maps of two whole 4x4 tiles per phase: F(4x4,3x3)
+            return ops.winograd4_conv(xin, eng.winograd_filter(self, False, scale, points=36), out, spec.branches[0][2], shift,
+                                      self.relu, bits_out=bits)
         if res is None and ops.winograd_routed(spec, False, Nb, H, W):
             # wide dilated 3x3 (layer4 conv2): F(2x2,3x3) around one batched launch of sixteen 1x1 GEMMs, 2.25 x fewer multiplies
             return ops.winograd_conv(xin, eng.winograd_filter(self, False, scale), out, spec.branches[0][2], shift, self.relu,
@@ -137,8 +141,12 @@ class ConvOp:
             else:
                 mask = (bp.relu_pattern(self.src, spec.cin, spec.cout) if spec.stride == 1 else bp.acts[self.src]) if relu else None
                 OH, OW = dz.shape[2:]
-                if bp.g.get(self.src) is None and (mask is None or isinstance(mask, ops.ReluBits)) \
-                        and ops.winograd_routed(spec, True, dz.shape[0], OH, OW):
+                wino_ok = bp.g.get(self.src) is None and (mask is None or isinstance(mask, ops.ReluBits))
+                if wino_ok and ops.winograd4_routed(spec, True, dz.shape[0], OH, OW, True):
+                    dx = torch.empty((dz.shape[0], spec.cin, H, W), dtype=torch.float32, device=dz.device)
+                    bp.g[self.src] = ops.winograd4_conv(dz, eng.winograd_filter(self, True, scale, points=36), dx, spec.branches[0][2],
+                                                        mask_bits=mask)
+                elif wino_ok and ops.winograd_routed(spec, True, dz.shape[0], OH, OW):
                     dx = torch.empty((dz.shape[0], spec.cin, H, W), dtype=torch.float32, device=dz.device)
                     bp.g[self.src] = ops.winograd_conv(dz, eng.winograd_filter(self, True, scale), dx, spec.branches[0][2],
                                                        mask_bits=mask)
@@ -598,15 +606,17 @@ class Engine:
             return op.expanded.pack(weights, transposed, out=old)
         return ops.conv_pack(op.spec, weights, transposed, scale, out=old, order=ops.gemm_order(op.spec, transposed))
 
-    def winograd_filter(self, op, transposed, scale=None):
-        """Transformed filter (16 packed point matrices) of a conv routed to the Winograd path: cached like `packed`, on the
-        same key -- rebuilt when the weights or the folded scale change, so a teacher's stays put between EMA updates."""
-        return self._cached(self._packs, (id(op), transposed, "winograd"), _pack_key(op, scale), self._build_winograd_filter,
-                            op, transposed, scale)
+    def winograd_filter(self, op, transposed, scale=None, points=16):
+        """Transformed filter (16 packed point matrices; points = 36: the F(4x4,3x3) form) of a conv routed to the Winograd path:
+        cached like `packed`, on the same key -- rebuilt when the weights or the folded scale change, so a teacher's stays put
+        between EMA updates.  The two forms have slots of their own (a layer may run both, on maps of different sizes)."""
+        slot = (id(op), transposed, "winograd") if points == 16 else (id(op), transposed, "winograd", points)
+        return self._cached(self._packs, slot, _pack_key(op, scale), self._build_winograd_filter, op, transposed, scale, points)
 
     @staticmethod
-    def _build_winograd_filter(old, op, transposed, scale):
-        return ops.winograd_filter(op.spec, op.convs[0].weight.detach(), transposed, scale, out=old)
+    def _build_winograd_filter(old, op, transposed, scale, points):
+        build = ops.winograd_filter if points == 16 else ops.winograd4_filter
+        return build(op.spec, op.convs[0].weight.detach(), transposed, scale, out=old)
 
     def largest_tensor_bytes(self, Nb, H, W):
         """Bytes of the largest activation (or expanded-conv intermediate) a pass over an [Nb, *, H, W] input creates.  The conv

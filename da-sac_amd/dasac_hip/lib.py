@@ -99,6 +99,8 @@ PROTOTYPES = {
     "dasac_winograd4_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "dasac_winograd4_grad_input": (_i, [_p, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "dasac_winograd4_wgrad_finish": (_i, [_p, _sz, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "dasac_winograd4_filter": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "dasac_winograd4_output": (_i, [_p, _sz, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
     "dasac_conv_pack_expanded":(_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dasac_tap_gather": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p]),
     "dasac_tap_scatter": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),

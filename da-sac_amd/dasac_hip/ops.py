@@ -318,7 +318,8 @@ def conv_dgrad(spec, dz, weights, in_hw, scale=None, res=None, mask=None, table=
 # Winograd F(2x2,3x3) for the wide dilated 3x3 convolutions (include/dasac_hip.h: dasac_winograd_*)
 # ----------------------------------------------------------------------------------------------
 # Algorithm of the forward / data-gradient / weight-gradient GEMMs of an eligible convolution:
-#   "auto"    Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2) and, for the weight gradient,
+#   "auto"    Winograd F(4x4,3x3) where `winograd4_routed` says so (on large maps layer4's conv2 data gradient and no-grad forward, layer3's no-grad forward), else
+#             Winograd F(2x2,3x3) where `winograd_routed` says so (layer4's 512 -> 512 dilated conv2) and, for the weight gradient,
 #             where `winograd4_wgrad_routed` (F(4x4,3x3): the same layers on large maps) or `winograd_wgrad_routed` does (layer4's
 #             and layer3's conv2), direct elsewhere;
 #   "direct"  the direct implicit GEMM everywhere.
@@ -432,6 +433,96 @@ def winograd_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, b
     return winograd_output(y, out, dilation, shift, relu, mask_bits, bits_out)
 
 
+# The same forward / data gradient as F(4x4,3x3) (the weight gradient's evaluation points, so `dasac_winograd4_input` serves x, dz and
+# the weight gradient alike): 36 point products per 16 outputs against 64, transformed tensors of 0.59 times the size, at 2 - 4 x the
+# direct kernel's rounding error against float64 (tests/test_gpu_winograd4_conv.py prints the ratio).  Routed per
+# (Cin, Cout, dilation, data gradient?, grad-enabled pass?) where the per-conv gain AND the end-to-end accuracy bounds of
+# tests/test_gpu_fullres.py were measured to hold (profiles/winograd4_conv_ab.txt, profiles/EXPERIMENTS.md); anything else keeps
+# F(2x2) or the direct GEMM.  Layer3's 256 -> 256 is routed in no-grad forwards only (the teacher, inference): a grad-enabled pass
+# keeps the direct launches tests/test_gpu_fullres.py counts.  Layer4's forward is routed in no-grad passes only as well: in a
+# grad-enabled pass its 4 x larger difference to the direct kernel flips more ReLUs that sit at zero, each of which moves a gradient
+# row by about 1e-2 of its maximum, and tests/test_gpu_winograd4_wgrad.py (512 planes at 2 x 33 x 33, auto against direct, bound 1e-3)
+# measured 1.6e-2 with it and 3.8e-6 without.  VGG16's undilated 512 -> 512 layers were not measured, so the table carries the dilation.
+WINOGRAD4_ROUTES = {
+    (512, 512, 4, True, True),       # (a) layer4 conv2, data gradient
+    (512, 512, 4, False, False),     # (b) layer4 conv2, forward of a no-grad pass (of a grad-enabled pass: not routed, see above)
+    (256, 256, 2, False, False),     # (c) layer3 conv2, no-grad forward
+}
+
+
+def winograd4_routed(spec, transposed, Nb, H, W, grad):
+    """The engine's rule for the F(4x4,3x3) forward (transposed: data gradient), consulted before `winograd_routed`: eligible, an
+    output width the batched point GEMMs take (padded M a multiple of 128: there is no 36-launch form), at least
+    WINOGRAD4_MIN_SAMPLES samples per phase and axis, the transformed tensors inside the 4 GiB window, and a route of the table.
+    grad: the pass records what a backward needs (ConvOp.forward's `keep`; always True for the data gradient)."""
+    if ALGORITHM != "auto" or not winograd_ok(spec, transposed):
+        return False
+    d = spec.branches[0][2]
+    if (spec.cin, spec.cout, d, bool(transposed), bool(grad)) not in WINOGRAD4_ROUTES:
+        return False
+    lib = L.load()
+    if lib.dasac_conv_mpad(spec.cin if transposed else spec.cout) % 128:
+        return False
+    if H // d < WINOGRAD4_MIN_SAMPLES or W // d < WINOGRAD4_MIN_SAMPLES:
+        return False
+    T = lib.dasac_winograd4_tiles(Nb, H, W, d)
+    return T > 0 and 144 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES
+
+
+def winograd4_filter(spec, weight, transposed, scale=None, out=None):
+    """U [36, Kpad, Mpad]: `winograd_filter` in the F(4x4,3x3) form, the 36 point matrices G g G^T with the 6x3 G."""
+    lib = L.load()
+    L.require_gpu(weight, scale)
+    M, K = (spec.cin, spec.cout) if transposed else (spec.cout, spec.cin)
+    shape = (36, lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M))
+    if out is None or tuple(out.shape) != shape:
+        out = torch.empty(shape, dtype=torch.float32, device=weight.device)
+    L.check(lib.dasac_winograd4_filter(_c(weight).data_ptr(), L.ptr(scale), spec.cout, spec.cin, int(transposed), out.data_ptr(),
+                                       L.stream_ptr()), "dasac_winograd4_filter")
+    return out
+
+
+def winograd4_output(y, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
+    """out [Nb,M,H,W] = epilogue(A^T Y A) of the point GEMMs' results y [36, M, T]; the epilogue of `winograd_output`."""
+    lib = L.load()
+    L.require_gpu(y, out, shift)
+    Nb, M, H, W = out.shape
+    assert y.is_contiguous() and out.is_contiguous() and y.dtype == torch.float32
+    for b in (mask_bits, bits_out):
+        assert b is None or b.shape == tuple(out.shape)
+    with PROFILE.span("winograd4_output", 0.0, None, 4.0 * (y.numel() + out.numel())):
+        L.check(lib.dasac_winograd4_output(y.data_ptr(), y.numel() * 4, Nb, M, H, W, int(dilation), L.ptr(shift), int(relu),
+                                           0 if mask_bits is None else mask_bits.words.data_ptr(),
+                                           0 if bits_out is None else bits_out.words.data_ptr(), out.data_ptr(), L.stream_ptr()),
+                "dasac_winograd4_output")
+    return out
+
+
+def winograd4_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
+    """`winograd_conv` in the F(4x4,3x3) form with u = `winograd4_filter`: the 6x6-patch input transform, ONE batched launch of the
+    36 point GEMMs (M padded to a multiple of 128 only), the output transform.  V [36, C, T] and Y [36, M, T] live in the stream's
+    scratch buffer; T counts the tiles rounded up to a multiple of 4, the padding tiles zero in V and never read from Y."""
+    lib = L.load()
+    L.require_gpu(x, u, out)
+    Nb, C, H, W = x.shape
+    M = out.shape[1]
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (Nb, M, H, W)
+    assert tuple(u.shape) == (36, lib.dasac_conv_kpad(C), lib.dasac_conv_mpad(M)) and u.is_contiguous()
+    if lib.dasac_conv_mpad(M) % 128 != 0:
+        raise L.DasacError("winograd4_conv: {} output channels have no batched point GEMM".format(M))
+    T = lib.dasac_winograd4_tiles(Nb, H, W, int(dilation))
+    if T <= 0 or 144 * max(C, M) * T > _MAX_TENSOR_BYTES:
+        raise L.DasacError("winograd4_conv: [36, {}, tiles] exceeds the 4 GiB buffer-descriptor window".format(max(C, M)))
+    v_elems, y_elems = 36 * C * T, 36 * M * T
+    ws = L.workspace(4 * (v_elems + y_elems), x.device)[:4 * (v_elems + y_elems)].view(torch.float32)
+    v, y = ws[:v_elems].view(36, C, T), ws[v_elems:v_elems + y_elems].view(36, M, T)
+    with PROFILE.span("winograd4_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
+        L.check(lib.dasac_winograd4_input(x.data_ptr(), Nb, C, H, W, int(dilation), v.data_ptr(), v_elems * 4, L.stream_ptr()),
+                "dasac_winograd4_input")
+    conv_gemm_batched(v.view(36, 1, C, 1, T), u, _winograd_table(C, T, x.device), y.view(36, 1, M, 1, T), (1, T), 1, M, C)
+    return winograd4_output(y, out, dilation, shift, relu, mask_bits, bits_out)
+
+
 # The weight gradient of the same convolutions has its own threshold: it is routed where it measured faster on its own, whatever the
 # forward and the data gradient of the layer do -- layer4's 512 -> 512 (2.80 -> 1.64 ms per conv) AND layer3's 256 -> 256 (0.714 ->
 # 0.520 ms; profiles/winograd_wgrad_ab.txt): no test counts conv_wgrad launches.
@@ -487,7 +578,7 @@ def winograd_wgrad(spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=N
 
 # The same weight gradient as F(4x4,3x3) (evaluation points 0, 1, -1, 2, -1/2, inf): 36 point products per 4x4-output tile against
 # 4 x 16, and transformed tensors of 0.59 times the size, at a few times the rounding error -- which a weight gradient, a terminal
-# sum, can take and the forward and the data gradient (ReLU patterns, pseudo-label thresholds) cannot.  Routed per layer where it
+# sum, takes everywhere; the forward and the data gradient take it per measured route (WINOGRAD4_ROUTES above).  Routed per layer where it
 # measured faster than the F(2x2) form on its own (profiles/winograd4_wgrad_ab.txt): a (Cin, Cout) pair missing here stays F(2x2).
 WINOGRAD4_WGRAD_LAYERS = {(256, 256), (512, 512)}
 WINOGRAD4_MIN_SAMPLES = 8                    # per phase and axis: two whole four-output tiles; below that most of a tile is overhang

@@ -255,7 +255,7 @@ int dasac_winograd_wgrad_finish(const void* workspace, size_t ws_bytes, int M, i
                                 float* dw, float* dot, float* sum_dz, dasac_stream_t stream);
 /* The same weight gradient as Winograd F(4x4,3x3), evaluation points 0, 1, -1, 2, -1/2, inf: 36 point products per 4x4-output tile,
  * 1.71 x fewer multiplies than the F(2x2) form on large maps, at a few times its rounding error (a weight gradient is a terminal
- * sum; the forward and the data gradient have no such form here).  The phases are cut into 4x4-output tiles, and
+ * sum; the forward and the data gradient in this form follow below).  The phases are cut into 4x4-output tiles, and
  * T = dasac_winograd4_tiles(Nb, H, W, dilation) is their count ROUNDED UP to a multiple of 4 (what dasac_conv_wgrad_batched needs);
  * both transforms write the padding tiles as zeros at all 36 points.
  *   dasac_winograd4_input        v [36][C][T] = B^T d B of every tile's 6x6 patch of x.  v_bytes >= 36*C*T*4.
@@ -271,6 +271,18 @@ int dasac_winograd4_grad_input(const float* dz, int Nb, int M, int H, int W, int
                                dasac_stream_t stream);
 int dasac_winograd4_wgrad_finish(const void* workspace, size_t ws_bytes, int M, int C, int T, const float* w, const float* scale,
                                  float* dw, float* dot, float* sum_dz, dasac_stream_t stream);
+/* Forward and data gradient of the same convolutions as F(4x4,3x3), same points: 36 products per 16 outputs where F(2x2) spends 64,
+ * at 2 - 4 x the direct kernel's rounding error.  The twins of the F(2x2) entry points around dasac_winograd4_input (x in the
+ * forward, dz in the data gradient) and ONE dasac_conv_gemm_batched launch of 36 entries (strides C*T, Kpad*Mpad, M*T):
+ *   dasac_winograd4_filter  u = 36 packed matrices, point pt = 6a + b, U[pt] = (G g G^T)[a][b]; modes as dasac_winograd_filter.
+ *   dasac_winograd4_output  out [Nb,M,H,W] = epi(A^T Y A) of y [36][M][T], epilogue operands as dasac_winograd_output.  The padding
+ *                           tiles and the outputs of a tile that hang over the map edge store nothing.  relu_bits_out is packed
+ *                           from the stored output by a second launch (the transform's lanes run along tiles, not pixels: no
+ *                           ballot), every word written.  y_bytes >= 36*M*T*4. */
+int dasac_winograd4_filter(const float* w, const float* scale, int Cout, int Cin, int transposed, float* u,
+                           dasac_stream_t stream);
+int dasac_winograd4_output(const float* y, size_t y_bytes, int Nb, int M, int H, int W, int dilation, const float* shift,
+                           int relu, const uint32_t* mask_bits, uint32_t* relu_bits_out, float* out, dasac_stream_t stream);
 
 /* Tap-expanded evaluation of few-output-channel, many-tap convolutions -- the ASPP classifiers
  * (deeplabv2.py:101-116): Y[(tap,co)] = 1x1 GEMM over taps*Cp channels (dasac_conv_gemm with weights

@@ -8,7 +8,8 @@ Per repetition: `iters` back-to-back evaluations between one HIP event pair -> m
 the direct one (input transform + the 16 point GEMMs, as one batched launch or as 16 + output transform; weight gradient: both
 transforms + the batched point contraction + finish, against conv_wgrad + its finish).  A second pass splits
 the Winograd time per kernel with an event pair per launch (ops.PROFILE); the weight gradient has a second Winograd leg, F(4x4,3x3)
-(ops.winograd4_wgrad), with its own split.  With DASAC_LIB naming an older build of the library
+(ops.winograd4_wgrad), with its own split, and so have the forward and the data gradient (ops.winograd4_conv; the forward also
+without recorded bits, as a no-grad pass runs it).  With DASAC_LIB naming an older build of the library
 the figures are that build's (the A/B against the parent commit on the same box): --direct-only for its direct GEMM,
 --gemm-schedule 2 for the 16-launch form an older build has."""
 import argparse
@@ -79,6 +80,13 @@ def main():
             sfx = "" if len(scheds) == 1 else " (--gemm-schedule {})".format(v)
             legs["forward winograd" + sfx] = lambda sched=sched: ops.winograd_conv(x, u_f, out, d, shift, True, bits_out=bits, gemm_schedule=sched)
             legs["dgrad   winograd" + sfx] = lambda sched=sched: ops.winograd_conv(dz, u_t, dx, d, mask_bits=mask, gemm_schedule=sched)
+        if hasattr(L.load(), "dasac_winograd4_output") and L.load().dasac_conv_mpad(C) % 128 == 0:       # absent from an older build
+            u4_f, u4_t = ops.winograd4_filter(spec, w, False, scale), ops.winograd4_filter(spec, w, True, scale)
+            legs["forward winograd F(4x4)"] = lambda: ops.winograd4_conv(x, u4_f, out, d, shift, True, bits_out=bits)
+            legs["forward winograd F(4x4), no bits (no-grad pass)"] = lambda: ops.winograd4_conv(x, u4_f, out, d, shift, True)
+            legs["dgrad   winograd F(4x4)"] = lambda: ops.winograd4_conv(dz, u4_t, dx, d, mask_bits=mask)
+            legs["filter transform F(4x4) (per weight update, forward + dgrad)"] = lambda: (
+                ops.winograd4_filter(spec, w, False, scale, out=u4_f), ops.winograd4_filter(spec, w, True, scale, out=u4_t))
         if hasattr(L.load(), "dasac_conv_wgrad_batched"):      # absent from an older build named by DASAC_LIB
             legs["wgrad   winograd"] = lambda: ops.winograd_wgrad(spec, dz, x, w, scale=scale, dot=dot, sum_dz=sums, out=dw)
         if hasattr(L.load(), "dasac_winograd4_wgrad_finish"):

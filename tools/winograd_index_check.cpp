@@ -1,5 +1,5 @@
 // Stand-alone host check of csrc/winograd_index.hpp: walks every offset the input and the output transform of winograd.hip form
-// (and, with four outputs per tile, the input and the grad transform of the F(4x4,3x3) weight gradient: check_shape4)
+// (and, with four outputs per tile, the input, the grad and the output transform of the F(4x4,3x3) paths: check_shape4)
 // for a list of shapes and requires each to lie inside its tensor, the tile numbering to be a bijection, and every output pixel
 // to belong to exactly one (tile, ey, ex).  Small shapes also touch heap arrays of the tensors' exact sizes at those offsets, so a
 // build with -fsanitize=address,undefined reports any access the arithmetic check itself would have missed.
@@ -271,6 +271,55 @@ static void check_shape4(int N, int C, int M, int H, int W, int d, bool say = tr
         }
     }
   for (size_t i = 0; i < owned.size(); ++i) EXPECT(owned[i] == 1, "m=4 pixel %zu belongs to %d tiles", i, owned[i]);
+  // ---- output_transform4 (forward / data gradient): per (m, real tile) 36 loads of y [36][M][T], and per in-image output one store
+  // and one load of its word of the masks [M][w32] (relu_bits_pack forms the same word offsets from the pixel index); every element
+  // of out and every pixel's bit exactly once, the padding tiles nothing
+  {
+    const int npix = N * H * W, w32 = (npix + 31) / 32;
+    const long long y_bytes = m_bytes, out_bytes = dz_bytes, bits_bytes = 4ll * M * w32;
+    std::vector<unsigned char> Y, O;
+    std::vector<unsigned> bits;
+    if (touch) {
+      Y.assign(y_bytes, 0);
+      O.assign(out_bytes, 0);
+      bits.assign((size_t)M * w32, 0u);
+    }
+    for (int m : ms)
+      for (int tile = 0; tile < g.T; ++tile) {
+        if (!real_tile(g, tile)) continue;
+        int n, y0, x0;
+        tile_origin<4>(g, tile, n, y0, x0);
+        for (int pt = 0; pt < 36; ++pt) {
+          const unsigned off = point_offset(g, M, pt, m, tile);
+          EXPECT((long long)off + 4 <= y_bytes && off % 4 == 0, "m=4 y offset %u of %lld", off, y_bytes);
+          if (touch && (long long)off + 4 <= y_bytes) ++Y[off];
+        }
+        for (int ey = 0; ey < 4; ++ey)
+          for (int ex = 0; ex < 4; ++ex) {
+            const int y = y0 + ey * d, x = x0 + ex * d;
+            if (!(y < H && x < W)) continue;                 // the kernel's `in`: an overhanging output stores nothing
+            const int rem = y * W + x, pix = n * H * W + rem;
+            const unsigned off = out_offset(g, M, n, m, rem);
+            EXPECT((long long)off + 4 <= out_bytes && off == 4u * (unsigned)((n * M + m) * H * W + rem), "m=4 out offset %u of %lld", off, out_bytes);
+            if (touch && (long long)off + 4 <= out_bytes) {
+              EXPECT(O[off] == 0, "m=4 out offset %u written twice", off);
+              O[off] = 1;
+            }
+            const unsigned boff = out_bits_offset(m, w32, pix);
+            EXPECT((long long)boff + 4 <= bits_bytes && boff == 4u * (unsigned)(m * w32 + pix / 32), "m=4 bit word offset %u of %lld", boff, bits_bytes);
+            if (touch && (long long)boff + 4 <= bits_bytes) {
+              EXPECT(!(bits[boff / 4] >> (pix & 31) & 1u), "m=4 bit of pixel %d named twice", pix);
+              bits[boff / 4] += 1u << (pix & 31);
+            }
+          }
+      }
+    if (touch) {
+      for (long long i = 0; i < out_bytes; i += 4) EXPECT(O[i] == 1, "m=4 out offset %lld never written", i);
+      for (int m = 0; m < M; ++m)
+        for (int p = 0; p < w32 * 32; ++p)
+          EXPECT((bits[(size_t)m * w32 + p / 32] >> (p & 31) & 1u) == (p < npix ? 1u : 0u), "m=4 bit %d of channel %d", p, m);
+    }
+  }
   if (touch) {
     for (long long i = 0; i < v_bytes; i += 4) EXPECT(V[i] == 1, "m=4 v offset %lld never written", i);
     for (long long i = 0; i < m_bytes; i += 4) EXPECT(Mt[i] == 1, "m=4 dm offset %lld never written", i);
@@ -302,7 +351,10 @@ int main() {
   const long long bad2 = g_bad;
   const int shapes4[][6] = {{3, 128, 128, 8, 8, 1}, {2, 128, 128, 9, 11, 1}, {1, 128, 256, 17, 19, 2}, {1, 256, 128, 33, 35, 4},
                             {1, 128, 128, 5, 7, 2}, {1, 256, 256, 17, 17, 2}, {2, 512, 512, 33, 33, 4}, {8, 256, 256, 97, 97, 2},
-                            {8, 512, 512, 97, 97, 4}, {1, 512, 512, 97, 97, 4}};
+                            {8, 512, 512, 97, 97, 4}, {1, 512, 512, 97, 97, 4},
+                            // tests/test_gpu_winograd4_conv.py, forward and data gradient (channel counts swapped)
+                            {1, 16, 128, 9, 8, 1}, {1, 128, 16, 9, 8, 1}, {1, 32, 128, 17, 19, 1}, {1, 128, 32, 17, 19, 1},
+                            {3, 48, 256, 21, 23, 2}, {3, 256, 48, 21, 23, 2}, {2, 64, 128, 33, 35, 4}, {2, 128, 64, 33, 35, 4}};
   for (const auto& s : shapes4) check_shape4(s[0], s[1], s[2], s[3], s[4], s[5]);
   const int extents[] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 15, 16, 17, 19, 20, 21, 32, 33, 35, 97};
   for (int d : {1, 2, 4})
