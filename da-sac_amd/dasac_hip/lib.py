@@ -116,6 +116,12 @@ PROTOTYPES = {
     "dasac_view_consistency": (_i, [_p, _i, _i, _i, _l, _f, _p, _p, _p, _p]),
     "dasac_boundary_counts_workspace": (_sz, [_i, _i, _i, _i]),
     "dasac_boundary_counts": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "dasac_label_segments_workspace": (_sz, [_i, _i, _i]),
+    "dasac_label_segments": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "dasac_segment_counts_workspace": (_sz, [_i, _i, _i, _i]),
+    "dasac_segment_counts": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "dasac_segment_filter_workspace": (_sz, [_i, _i, _i]),
+    "dasac_segment_filter": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "dasac_crf_meanfield_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "dasac_crf_meanfield": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "dasac_label_hist": (_i, [_p, _i, _l, _p, _p]),

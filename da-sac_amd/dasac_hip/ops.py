@@ -1401,7 +1401,7 @@ def label_hist(labels_u8, counts=None):
 MASK_COUNTS_MAX_SCORES, MASK_COUNTS_MAX_MAPS = 4, 2
 
 
-# What `mask_counts`, `confusion_counts` and `boundary_counts` check alike, in the order they check it: _count_front, the class count
+# What `mask_counts`, `confusion_counts`, `boundary_counts` and `segment_counts` check alike, in the order they check it: _count_front, the class count
 # (_count_classes), then _count_layers; a wrapper's own checks go between them.
 def _count_front(op, scores, label_maps, gt, *outs):
     """The layer lists and the ground truth: (scores, label_maps, B, H, W)."""
@@ -1535,6 +1535,101 @@ def boundary_counts(scores, label_maps, gt, table=None, radius=8, ignore_index=2
     L.check(lib.dasac_boundary_counts(*sp, *mp, u8_mask, gt.data_ptr(), B, Cn, H, W, radius, int(ignore_index), table.data_ptr(),
                                       ws.data_ptr(), ws.numel(), L.stream_ptr()), "dasac_boundary_counts")
     return table
+
+
+SEGMENT_BINS = 24                                           # DASAC_SEGMENT_BINS
+SEGMENT_ROWS = ("segments", "pixels", "matched_pixels", "matched_segments")     # dimension 3 of a segment table
+SEGMENT_TILE = (32, 64)                                     # csrc/segments_index.hpp: kTileH x kTileW, where the kernels' seams lie
+SEGMENT_MAX_CLASSES, SEGMENT_COUNTS_MAX_CLASSES = 255, 64
+
+
+def _segment_gpu(op, *tensors):
+    """L.require_gpu with the op's name in front of the refusal."""
+    try:
+        L.require_gpu(*tensors)
+    except L.DasacError as exc:
+        raise L.DasacError("{}: {}".format(op, exc)) from None
+
+
+def _segment_map(op, labels, num_classes, connectivity, limit=SEGMENT_MAX_CLASSES):
+    """What the segment ops check of a label map alike: (contiguous labels, B, H, W, C, connectivity)."""
+    _segment_gpu(op, labels)
+    if labels.dtype not in (torch.int64, torch.uint8) or labels.dim() != 3 or labels.numel() == 0:
+        raise L.DasacError("{}: labels must be a non-empty int64 or uint8 [B,H,W] map (got {} {})".format(op, labels.dtype, tuple(labels.shape)))
+    Cn, connectivity = int(num_classes), int(connectivity)
+    if not 1 <= Cn <= limit:
+        raise L.DasacError("{}: num_classes must be in 1..{} (got {})".format(op, limit, Cn))
+    if connectivity not in (4, 8):
+        raise L.DasacError("{}: connectivity must be 4 or 8 (got {})".format(op, connectivity))
+    B, H, W = labels.shape
+    if H * W > 2 ** 31 - 1:
+        raise L.DasacError("{}: an image of {} x {} pixels is larger than 2^31 - 1".format(op, H, W))
+    return _c(labels), B, H, W, Cn, connectivity
+
+
+def label_segments(labels, num_classes, connectivity=8, want_size=True):
+    """Connected components of a label map (include/dasac_hip.h: dasac_label_segments).  labels: int64 or uint8 [B,H,W]; a value in
+    [0, num_classes) is a class, anything else (255, -1) no class.  Returns (segment, size): int32 [B,H,W] each -- the root (smallest
+    y*W + x) of the pixel's segment under `connectivity` 4 or 8, -1 where the pixel holds no class, and the pixel count of that
+    segment, 0 there; size is None unless `want_size`.  The images of a batch do not see each other."""
+    lib = L.load()
+    labels, B, H, W, Cn, connectivity = _segment_map("label_segments", labels, num_classes, connectivity)
+    segment = torch.empty((B, H, W), dtype=torch.int32, device=labels.device)
+    size = torch.empty((B, H, W), dtype=torch.int32, device=labels.device) if want_size else None
+    ws = L.workspace(lib.dasac_label_segments_workspace(B, H, W), labels.device)
+    L.check(lib.dasac_label_segments(labels.data_ptr(), int(labels.dtype == torch.uint8), B, Cn, H, W, connectivity, segment.data_ptr(),
+                                     L.ptr(size), L.ptr(ws), ws.numel(), L.stream_ptr()), "dasac_label_segments")
+    return segment, size
+
+
+def segment_counts(scores, label_maps, gt, table=None, connectivity=8, ignore_index=255, num_classes=None):
+    """Object-level validation tables (include/dasac_hip.h: dasac_segment_counts).  scores: up to 4 fp32 [B,C,H,W] tensors (arg-max,
+    first maximum wins); label_maps: up to 2 [B,H,W] maps, int64 or uint8 each (255 = no label); gt int64 [B,H,W].  Accumulates into
+    `table` (int64 [L,2,SEGMENT_BINS,4,C], scores first, then label maps; allocated zeroed when None) and returns it: side 0 counts
+    the ground truth's segments, side 1 the predicted map's, each in the bin floor(log2(size)) of its size (the last bin takes
+    everything larger); rows SEGMENT_ROWS -- segments, their counted pixels, the pixels of them the other map gives the same class,
+    and the segments where those are more than half (objects found / segments that are real).  With label maps only, C comes from
+    `table` or `num_classes`.  driver.summarise_segments reads the tables."""
+    lib = L.load()
+    op = "segment_counts"
+    _segment_gpu(op, gt, table, *(scores or ()), *(label_maps or ()))
+    scores, label_maps, B, H, W = _count_front(op, scores, label_maps, gt, table)
+    if table is not None and (table.dtype != torch.int64 or table.dim() != 5):
+        raise L.DasacError("segment_counts accumulates into an int64 [L,2,{},4,C] tensor (got {} {})".format(SEGMENT_BINS, table.dtype, tuple(table.shape)))
+    Cn = _count_classes(op, scores, lambda: table.shape[4] if table is not None else num_classes, "table")
+    connectivity = int(connectivity)
+    if connectivity not in (4, 8) or not 1 <= Cn <= SEGMENT_COUNTS_MAX_CLASSES:
+        raise L.DasacError("segment_counts: connectivity must be 4 or 8 and C in 1..{} (got {} and {})".format(
+            SEGMENT_COUNTS_MAX_CLASSES, connectivity, Cn))
+    scores, label_maps, gt, sp, mp, u8_mask = _count_layers(op, scores, label_maps, gt, B, Cn, H, W, (torch.int64, torch.uint8))
+    n_layers = len(scores) + len(label_maps)
+    shape = (n_layers, 2, SEGMENT_BINS, len(SEGMENT_ROWS), Cn)
+    if table is None:
+        table = torch.zeros(shape, dtype=torch.int64, device=gt.device)
+    elif tuple(table.shape) != shape or not table.is_contiguous():
+        raise L.DasacError("segment_counts accumulates into a contiguous int64 {} tensor (got {} {})".format(shape, table.dtype, tuple(table.shape)))
+    need = lib.dasac_segment_counts_workspace(n_layers, B, H, W)
+    ws = L.workspace(need, gt.device)
+    L.check(lib.dasac_segment_counts(*sp, *mp, u8_mask, gt.data_ptr(), B, Cn, H, W, connectivity, int(ignore_index), table.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), L.stream_ptr()), "dasac_segment_counts")
+    return table
+
+
+def segment_filter(labels, min_size, num_classes, fill=255, connectivity=8):
+    """A copy of the label map (int64 or uint8 [B,H,W]) in which every pixel of a segment smaller than `min_size` pixels holds `fill`
+    (include/dasac_hip.h: dasac_segment_filter); every other pixel, no-class pixels included, keeps its value, and min_size <= 1
+    copies the map.  The input is not written."""
+    lib = L.load()
+    labels, B, H, W, Cn, connectivity = _segment_map("segment_filter", labels, num_classes, connectivity)
+    fill = int(fill)
+    if labels.dtype == torch.uint8 and not 0 <= fill <= 255:
+        raise L.DasacError("segment_filter: fill {} does not fit a uint8 map".format(fill))
+    out = torch.empty_like(labels)
+    ws = L.workspace(lib.dasac_segment_filter_workspace(B, H, W), labels.device)
+    L.check(lib.dasac_segment_filter(labels.data_ptr(), int(labels.dtype == torch.uint8), B, Cn, H, W, connectivity,
+                                     max(-1, min(int(min_size), 2 ** 31 - 1)), fill, out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()),
+            "dasac_segment_filter")
+    return out
 
 
 CONSISTENCY_MAX_VIEWS, CONSISTENCY_MAX_CLASSES = 8, 32      # DASAC_CONSISTENCY_MAX_VIEWS; the kernel's class limit

@@ -10,8 +10,8 @@ import torch
 from reports import (  # noqa: F401  (the public surface of this module)
     activation_report, class_gap_report, class_subset_mean, counts_from_confusion, domain_gap_report, format_activation_report,
     format_boundary, format_class_gap_report, format_confusion, format_consistency, format_domain_gap_report, format_gradient_report,
-    gradient_report, moment_gap, pseudo_label_audit, skipped_step_report, stat_mean, summarise_boundary, summarise_confusion,
-    summarise_consistency, summarise_iou, summarise_reliability, summarise_validation)
+    format_segments, gradient_report, moment_gap, pseudo_label_audit, skipped_step_report, stat_mean, summarise_boundary,
+    summarise_confusion, summarise_consistency, summarise_iou, summarise_reliability, summarise_segments, summarise_validation)
 from visualise import FixedBatches  # noqa: F401  (`save_fixed_batch` / `has_fixed_batch`, base_trainer.py:200-218)
 
 
@@ -794,7 +794,8 @@ def _step_inputs(batch, step, group_size, num_groups, device, world):
 
 
 def validation(net, loader, step="source", group_size=None, max_iter=None, ignore_classes=(), num_classes=19, num_groups=None,
-               confusion=False, reliability_bins=0, consistency=False, consistency_cover=0.5, boundary_radius=0):
+               confusion=False, reliability_bins=0, consistency=False, consistency_cover=0.5, boundary_radius=0, segment_tables=False,
+               segment_connectivity=8):
     """`Trainer.validation` (train.py:339-469) with its step function (`step` :119-155 or `_step_target` :211-250, train=False):
     eval mode under no_grad (the previous mode is restored), loss means, one (tp, fp, fn) table per mask layer, the per-class and
     class-subset summaries and the checkpoint score.  Neither the teacher nor the class prior is updated.
@@ -840,7 +841,14 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     as `table` is and copied once.  The namespace's `boundary` is {layer: int64 [R+1,5,C]} on the host (slot = Chebyshev distance to
     the nearest class contour - 1, the last slot everything further; rows tp, fp, fn, pred, both) and `boundary_summary` is
     summarise_boundary of it at the radii 1, 2, 4, ... up to R: trimap-band, interior and Boundary IoU per class and layer
-    (format_boundary renders it); {} and None when off.  Reported only: every other field is the one of a run without it."""
+    (format_boundary renders it); {} and None when off.  Reported only: every other field is the one of a run without it.
+
+    On which objects the errors are, opt-in: with `segment_tables` one ops.segment_counts per batch runs beside the count pass on
+    the same layers (connected components under `segment_connectivity` 4 or 8) into one device table, which is summed over ranks
+    as `table` is -- its collective comes last -- and copied once.  The namespace's `segments` is {layer: int64 [2,24,4,C]} on the
+    host (side 0 the ground truth's segments, side 1 the predicted map's; bin floor(log2(size)); rows ops.SEGMENT_ROWS) and
+    `segment_summary` is summarise_segments of it: object recall, segment precision and fragmentation per size group and class
+    (format_segments renders it); {} and None when off.  Reported only: every other field is the one of a run without it."""
     from types import SimpleNamespace
     from dasac_hip import ops
     assert step in ("source", "target"), step
@@ -855,6 +863,7 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     layers, table, rows, keys, matrices, rel = None, None, [], None, None, None
     cons, cons_was = None, None
     radius, bound = int(boundary_radius), None
+    seg = None
     if consistency:
         cons_was = core.swap_consistency((True, consistency_cover, None))
     try:
@@ -883,18 +892,22 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
                     table = ops.mask_counts(scores, maps, gt, table, num_classes=num_classes)
                 if radius > 0:
                     bound = ops.boundary_counts(scores, maps, gt, bound, radius, num_classes=num_classes)
+                if segment_tables:
+                    seg = ops.segment_counts(scores, maps, gt, seg, segment_connectivity, num_classes=num_classes)
                 rows.append(torch.cat([losses[k].detach().mean().reshape(1) for k in keys]))
     finally:
         if consistency:
             cons = core.swap_consistency(cons_was)[2]
     if table is None:
         return SimpleNamespace(losses={}, counts={}, per_class={}, mean={}, checkpoint_score=0.0, confusion={}, reliability={},
-                               consistency={}, consistency_summary=None, boundary={}, boundary_summary=None)
+                               consistency={}, consistency_summary=None, boundary={}, boundary_summary=None, segments={},
+                               segment_summary=None)
     if consistency and cons is None:        # a rank that owns no group (views sharded over ranks) still takes part in the sum
         cons = ops.consistency_tables(num_classes, group_size, device)
     names = layers[0] + layers[1]
     loss_rows = torch.stack(rows)
-    # the collectives, in the one order every rank follows: counts, loss rows, consistency, boundary (rank_sum: nothing on one rank)
+    # the collectives, in the one order every rank follows: counts, loss rows, consistency, boundary, segments (rank_sum: nothing on
+    # one rank)
     table = rank_sum(table)
     if step == "target" and world > 1:
         loss_rows = rank_sum(loss_rows) / world
@@ -902,12 +915,19 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
         cons = ops.ConsistencyTables(rank_sum(cons.buffer), cons.C, cons.T)
     if bound is not None:
         bound = rank_sum(bound)
+    if seg is not None:
+        seg = rank_sum(seg)
     table, loss_rows = table.cpu(), loss_rows.cpu().tolist()
     bound_tables, bound_summary = {}, None
     if bound is not None:
         bound = bound.cpu()
         bound_tables = {name: bound[i] for i, name in enumerate(names)}
         bound_summary = summarise_boundary(bound_tables, ignore_classes, [r for r in (1, 2, 4, 8, 16) if r <= radius])
+    seg_tables, seg_summary = {}, None
+    if seg is not None:
+        seg = seg.cpu()
+        seg_tables = {name: seg[i] for i, name in enumerate(names)}
+        seg_summary = summarise_segments(seg_tables, ignore_classes)
     cons_tables, cons_summary = {}, None
     if consistency:
         cons = cons.cpu()
@@ -927,7 +947,17 @@ def validation(net, loader, step="source", group_size=None, max_iter=None, ignor
     losses = {k: stat_mean([row[i] for row in loss_rows]) for i, k in enumerate(keys)}
     return SimpleNamespace(losses=losses, counts=counts, per_class=per_class, mean=mean, checkpoint_score=score,
                            confusion=conf_tables, reliability=rel_tables, consistency=cons_tables, consistency_summary=cons_summary,
-                           boundary=bound_tables, boundary_summary=bound_summary)
+                           boundary=bound_tables, boundary_summary=bound_summary, segments=seg_tables, segment_summary=seg_summary)
+
+
+def despeckle(labels, min_size, num_classes=19, fill=255, connectivity=8):
+    """A copy of a TRAIN-ID label map (int64 or uint8 [B,H,W], 255 = no label) without its specks: every pixel of a connected
+    segment (one class, `connectivity` 4 or 8) of fewer than `min_size` pixels holds `fill`; ops.segment_filter on the device.  Meant
+    for the `teacher_labels` of a target step and for the maps of infer_label_maps / infer_label_maps_ms BEFORE a look-up table: a
+    map that went through a LUT holds dataset ids, which are no classes in [0, num_classes) -- it must not be passed (its ids above
+    num_classes would be left alone as "no class" and the others taken for the wrong classes' segments)."""
+    from dasac_hip import ops
+    return ops.segment_filter(labels, min_size, num_classes, fill, connectivity)
 
 
 # --------------------------------------------------------------------------------------------------

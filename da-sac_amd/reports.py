@@ -1,12 +1,15 @@
 """Host-side readers and text renderers of the small tables the device passes of driver.py produce: IoU and validation summaries,
 confusion and reliability tables, boundary tables, view consistency, gradient health, activation health, domain gap and
 class-conditional features.  Pure arithmetic and string formatting on the host: no network, no kernels.  driver.py re-exports
-every public name, and `driver.<name>` is how callers reach them."""
+every public name, and `driver.<name>` is how callers reach them.  The readers of the segment tables live in segment_reports.py
+and are part of this module's surface too."""
 import math
 from types import SimpleNamespace
 
 import numpy as np
 import torch
+
+from segment_reports import format_segments, summarise_segments  # noqa: F401  (the readers of the segment tables: part of this surface)
 
 
 def _ratio(num, den):

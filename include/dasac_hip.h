@@ -749,6 +749,58 @@ int dasac_boundary_counts(const float* scores0, const float* scores1, const floa
                           const void* labels0, const void* labels1, int labels_u8_mask, const int64_t* gt, int B, int C, int H,
                           int W, int R, int ignore_index, int64_t* table, void* workspace, size_t ws_bytes, dasac_stream_t stream);
 
+/* On which OBJECTS the errors are: connected-component labelling of a label map, the size-stratified segment tables built on it and
+ * the removal of specks; a diagnostic the reference does not have.
+ *   A MAP is one label per pixel.  Its class is the value itself when that lies in [0, C); every other value (255, -1, anything out
+ *   of range) is "no class".  Two pixels of one image are ADJACENT under connectivity 4 when they share an edge, under connectivity 8
+ *   when they share an edge or a corner.  A SEGMENT is a maximal set of pixels of the same class connected through adjacent pixels
+ *   of that class; no-class pixels belong to no segment.  The images of a batch do not see each other, and a run that ends at the
+ *   right edge of row y is not adjacent to one that starts at the left edge of row y + 1.  A segment's ROOT is the smallest y*W + x
+ *   among its pixels, its SIZE its pixel count, its BIN min(floor(log2(size)), DASAC_SEGMENT_BINS - 1).
+ *
+ * dasac_label_segments: labels int64 [B,H,W], or uint8 at any address when `labels_u8` is set.  segment: int32 [B,H,W], the root of
+ * the pixel's segment, -1 for a no-class pixel; size: int32 [B,H,W], the size of the pixel's segment, 0 for a no-class pixel; may be
+ * NULL.  1 <= C <= 255, connectivity 4 or 8, B, H, W >= 1, H*W <= 2^31 - 1; batch offsets are 64-bit.  Roots are canonical by
+ * definition, so the result is a function of the input alone: bit-identical from run to run whatever the block order.  It asks
+ * for no workspace (the parents are built in `segment`, the counts in `size`); at most four launches.
+ *
+ * dasac_segment_counts: the layer slots of dasac_boundary_counts (up to 4 fp32 score tensors, arg-max with the first maximum
+ * winning; up to 2 label maps, int64 or uint8 by `labels_u8_mask`; NULL slots skipped, layers numbered over the non-NULL slots,
+ * scores first); gt int64 [B,H,W]; 1 <= C <= 64.  table: int64 [L][2][DASAC_SEGMENT_BINS][4][C], ACCUMULATED into.  A ground-truth
+ * pixel equal to ignore_index is no-class in the ground-truth map, and that is checked first.  With g the ground truth and a the
+ * layer's prediction:
+ *   side 0, ground-truth segments (computed once per call, shared by all layers): for each segment S of class c, size s, bin b, with
+ *     m = #{p in S : a(p) == c}, at [layer][0][b][.][c]: row 0 += 1, row 1 += s, row 2 += m, row 3 += 1 when 2*m > s (the object
+ *     was found);
+ *   side 1, predicted segments, taken over the whole predicted map, ignored pixels included as members and neighbours: for each
+ *     segment S of class c, size s, bin b (binned by s), with n = #{p in S : g(p) != ignore_index} and m = #{p in S : g(p) == c
+ *     and not ignored}: a segment with n == 0 is counted nowhere; otherwise row 0 += 1, row 1 += n, row 2 += m, row 3 += 1 when
+ *     2*m > n (the segment is real, not a speck).
+ *   Summed over the bins these hold bit for bit against dasac_mask_counts: side 0 row 2 = tp, side 0 row 1 = tp + fn,
+ *   side 1 row 1 = tp + fp, side 1 row 2 = tp.
+ * The workspace holds dasac_segment_counts_workspace(layers, B, H, W) bytes (`layers` = the non-NULL slots) and is aligned to 16
+ * bytes; 4 + 4 L launches (one fewer per map when an image is a single tile: nothing to merge).
+ *
+ * dasac_segment_filter: `out` has the dtype and shape of `labels`; a pixel whose segment has size < min_size gets `fill` (which must
+ * fit the dtype), every other pixel, no-class pixels included, keeps its value; min_size <= 1 copies the map.  `out` may NOT
+ * alias or overlap `labels`: DASAC_EINVAL.  1 <= C <= 255.
+ *
+ * For all three: fp32 / int64 / int32 tensors are aligned to their element size; anything else is DASAC_EINVAL before any launch.
+ * Integer arithmetic only, exact and bit-identical from run to run; no load or store leaves a tensor or the workspace at any
+ * alignment of a uint8 map; no allocation, no synchronisation, and no kernel waits for another workgroup. */
+#define DASAC_SEGMENT_BINS 24
+size_t dasac_label_segments_workspace(int B, int H, int W);
+int dasac_label_segments(const void* labels, int labels_u8, int B, int C, int H, int W, int connectivity, int32_t* segment,
+                         int32_t* size, void* workspace, size_t ws_bytes, dasac_stream_t stream);
+size_t dasac_segment_counts_workspace(int layers, int B, int H, int W);
+int dasac_segment_counts(const float* scores0, const float* scores1, const float* scores2, const float* scores3,
+                         const void* labels0, const void* labels1, int labels_u8_mask, const int64_t* gt, int B, int C, int H,
+                         int W, int connectivity, int ignore_index, int64_t* table, void* workspace, size_t ws_bytes,
+                         dasac_stream_t stream);
+size_t dasac_segment_filter_workspace(int B, int H, int W);
+int dasac_segment_filter(const void* labels, int labels_u8, int B, int C, int H, int W, int connectivity, int min_size, int fill,
+                         void* out, void* workspace, size_t ws_bytes, dasac_stream_t stream);
+
 /* Mean-field refinement of an inference label map: a locally connected CRF (the ConvCRF form of Teichmann & Cipolla, 2018: truncated
  * Gaussian kernels on a dilated window, Potts compatibility) over the fused class probabilities and the image -- the step DeepLabv2's
  * published pipeline ends in; the reference only kept a place for it (infer_val.py:134).
