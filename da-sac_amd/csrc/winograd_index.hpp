@@ -14,9 +14,10 @@
 // adjacent floats, and the four taps of a patch row fill each other's gaps.
 //
 // Everything above is F(2,3) per axis.  The functions that depend on the outputs per tile take them as a template parameter TM
-// (2 by default: F(2x2,3x3); 4: the F(4x4,3x3) weight gradient): a phase of q samples has ceil(q / TM) tiles, tile (p, t) produces
-// the outputs o0 + e*d, e = 0 .. TM-1, o0 = p + TM*d*t, from the TM + 2 inputs o0 + (k - 1)*d, and the longer phases have a
-// leftover tile when q % TM == 0.  The structs are the same for both, so a kernel of either form takes a Geom by value.
+// (2 by default: F(2x2,3x3); 4: F(4x4,3x3) -- forward, data gradient and weight gradient have both forms): a phase of q samples has
+// ceil(q / TM) tiles, tile (p, t) produces the outputs o0 + e*d, e = 0 .. TM-1, o0 = p + TM*d*t, from the TM + 2 inputs
+// o0 + (k - 1)*d, and the longer phases have a leftover tile when q % TM == 0.  The structs are the same for both, so a kernel of
+// either form takes a Geom by value.  What else depends on TM stands under "the two forms" below.
 #pragma once
 #include <stdint.h>
 
@@ -47,6 +48,17 @@ DASAC_HD Div make_div(int d) {
 DASAC_HD int div(int n, Div f) {
   return f.mul ? (int)((unsigned)(((unsigned long long)(unsigned)n * f.mul) >> 32) >> f.shift) : n;
 }
+
+// ---- the two forms: everything beyond the tile arithmetic that depends on TM ------------------------------------------------------
+// points of a tile = entries of the batched point GEMMs: (TM + 2)^2 = 16 or 36
+template <int TM>
+constexpr int kPoints = (TM + 2) * (TM + 2);
+// F(4x4) pads the tile axis T of the transformed tensors to a multiple of 4 (the batched point contraction needs one, and 4x4 tiles
+// rarely give one); the padding tiles are zero at every point.  F(2x2) takes the tile count as it is.
+template <int TM>
+constexpr bool kPaddedT = TM == 4;
+template <int TM>
+DASAC_HD int64_t padded_tiles(int64_t tiles) { return kPaddedT<TM> ? (tiles + 3) / 4 * 4 : tiles; }
 
 struct Axis {
   int n, d;      // extent, dilation
@@ -97,8 +109,7 @@ struct Geom {
   Axis ay, ax;
   int N, H, W, HW;
   int tiles_img;          // ay.tiles * ax.tiles
-  int T;                  // the pixel axis of the point GEMMs.  TM == 2: N * tiles_img.  TM == 4: that rounded up to a multiple of 4
-                          // (the batched point contraction needs it); tiles N * tiles_img .. T-1 are padding, zero at every point
+  int T;                  // the pixel axis of the point GEMMs: padded_tiles(N * tiles_img); tiles N * tiles_img .. T-1 are padding
   Div by_tiles_img, by_tx, by_hw, by_w;
 };
 template <int TM = 2>
@@ -111,7 +122,7 @@ DASAC_HD Geom make_geom(int N, int H, int W, int d) {
   g.W = W;
   g.HW = H * W;
   g.tiles_img = g.ay.tiles * g.ax.tiles;
-  g.T = TM == 4 ? (N * g.tiles_img + 3) / 4 * 4 : N * g.tiles_img;
+  g.T = (int)padded_tiles<TM>(N * g.tiles_img);
   g.by_tiles_img = make_div(g.tiles_img);
   g.by_tx = make_div(g.ax.tiles);
   g.by_hw = make_div(g.HW);
@@ -151,7 +162,7 @@ DASAC_HD unsigned patch_offset(const Geom& g, int C, int n, int c, int y0, int x
   if ((unsigned)y >= (unsigned)g.H || (unsigned)x >= (unsigned)g.W) return kOutside;
   return (unsigned)((n * C + c) * g.HW + y * g.W + x) * 4u;
 }
-// byte offset into a transformed tensor [points][C][T] (V, dM, or the point GEMMs' output), pt < 16 or 36: (TM + 2)^2 points
+// byte offset into a transformed tensor [points][C][T] (V, dM, or the point GEMMs' output), pt < kPoints<TM>
 DASAC_HD unsigned point_offset(const Geom& g, int C, int pt, int c, int tile) { return (unsigned)((pt * C + c) * g.T + tile) * 4u; }
 // byte offset into an NCHW activation of M channels
 DASAC_HD unsigned out_offset(const Geom& g, int M, int n, int m, int rem) { return (unsigned)((n * M + m) * g.HW + rem) * 4u; }

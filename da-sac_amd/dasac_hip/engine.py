@@ -109,14 +109,11 @@ class ConvOp:
         if keep and self.relu and eng._bits_wanted[self.dst] and ops.bits_ok(spec.cout, spec.cin):
             bits = ops.ReluBits(Nb, spec.cout, OH, OW, xin.device)
             saved["bits"][self.dst] = bits
-        if res is None and ops.winograd4_routed(spec, False, Nb, H, W, keep):
-            # a route of ops.WINOGRAD4_ROUTES (no-grad passes of layer4's and layer3's conv2) on maps of two whole 4x4 tiles per phase: F(4x4,3x3)
-            return ops.winograd4_conv(xin, eng.winograd_filter(self, False, scale, points=36), out, spec.branches[0][2], shift,
-                                      self.relu, bits_out=bits)
-        if res is None and ops.winograd_routed(spec, False, Nb, H, W):
-            # wide dilated 3x3 (layer4 conv2): F(2x2,3x3) around one batched launch of sixteen 1x1 GEMMs, 2.25 x fewer multiplies
-            return ops.winograd_conv(xin, eng.winograd_filter(self, False, scale), out, spec.branches[0][2], shift, self.relu,
-                                     bits_out=bits)
+        form = ops.winograd_form(spec, False, Nb, H, W, keep) if res is None else None
+        if form is not None:
+            # wide dilated 3x3: F(4x4,3x3) on a route of ops.WINOGRAD4_ROUTES (no-grad passes of layer4's and layer3's conv2 on maps of two
+            # whole 4x4 tiles per phase), else F(2x2,3x3) (layer4 conv2), around one batched launch of the 1x1 point GEMMs
+            return form.conv(xin, eng.winograd_filter(self, False, scale, form), out, spec.branches[0][2], shift, self.relu, bits_out=bits)
         return ops.conv_gemm(xin, eng.packed(self, False, scale), eng.table(self, H, W, False, xin.device), out, (OH, OW),
                              spec.stride, spec.cout, spec.K, 1, shift, res, None, self.relu, bits_out=bits)
 
@@ -142,14 +139,10 @@ class ConvOp:
                 mask = (bp.relu_pattern(self.src, spec.cin, spec.cout) if spec.stride == 1 else bp.acts[self.src]) if relu else None
                 OH, OW = dz.shape[2:]
                 wino_ok = bp.g.get(self.src) is None and (mask is None or isinstance(mask, ops.ReluBits))
-                if wino_ok and ops.winograd4_routed(spec, True, dz.shape[0], OH, OW, True):
+                form = ops.winograd_form(spec, True, dz.shape[0], OH, OW, True) if wino_ok else None
+                if form is not None:
                     dx = torch.empty((dz.shape[0], spec.cin, H, W), dtype=torch.float32, device=dz.device)
-                    bp.g[self.src] = ops.winograd4_conv(dz, eng.winograd_filter(self, True, scale, points=36), dx, spec.branches[0][2],
-                                                        mask_bits=mask)
-                elif wino_ok and ops.winograd_routed(spec, True, dz.shape[0], OH, OW):
-                    dx = torch.empty((dz.shape[0], spec.cin, H, W), dtype=torch.float32, device=dz.device)
-                    bp.g[self.src] = ops.winograd_conv(dz, eng.winograd_filter(self, True, scale), dx, spec.branches[0][2],
-                                                       mask_bits=mask)
+                    bp.g[self.src] = form.conv(dz, eng.winograd_filter(self, True, scale, form), dx, spec.branches[0][2], mask_bits=mask)
                 else:
                     bp.g[self.src] = ops.conv_dgrad(spec, dz, None, (H, W), scale=scale, res=bp.g.get(self.src), mask=mask,
                                                     table=eng.table(self, OH, OW, True, dz.device),
@@ -192,14 +185,12 @@ class ConvOp:
                 dot = bp.dot_slice(spec, dz.device)
             if want_bn or want_bias:      # channel sums ride along with the wgrad kernel
                 sums = bp.sums_dest(b_idx, want_bias and bias_is_sums, spec.cout, dz.device)
-            if ops.winograd4_wgrad_routed(spec, xin.shape[0], xin.shape[2], xin.shape[3]):
-                # the same layers on maps of at least two whole 4x4-output tiles per phase: F(4x4,3x3), 1.71 x fewer multiplies again
-                bp.store(w_idx, [ops.winograd4_wgrad(spec, dz, xin, self.convs[0].weight.detach(), scale=scale, dot=dot, sum_dz=sums,
-                                                     out=bp.dest(w_idx[0]))])
-            elif ops.winograd_wgrad_routed(spec, xin.shape[0], xin.shape[2], xin.shape[3]):
-                # wide dilated 3x3 (conv2 of layer3 and layer4): the adjoint of the forward's F(2x2,3x3) form, 2.25 x fewer multiplies
-                bp.store(w_idx, [ops.winograd_wgrad(spec, dz, xin, self.convs[0].weight.detach(), scale=scale, dot=dot, sum_dz=sums,
-                                                    out=bp.dest(w_idx[0]))])
+            form = ops.winograd_wgrad_form(spec, xin.shape[0], xin.shape[2], xin.shape[3])
+            if form is not None:
+                # wide dilated 3x3 (conv2 of layer3 and layer4): the adjoint of the forward's Winograd form, 2.25 x fewer multiplies as
+                # F(2x2,3x3), 1.71 x fewer again as F(4x4,3x3) on maps of at least two whole 4x4-output tiles per phase
+                bp.store(w_idx, [form.wgrad(spec, dz, xin, self.convs[0].weight.detach(), scale=scale, dot=dot, sum_dz=sums,
+                                            out=bp.dest(w_idx[0]))])
             else:
                 bp.store(w_idx, ops.conv_wgrad(spec, dz, xin, [c.weight.detach() for c in self.convs], scale=scale, dot=dot,
                                                table=eng.table(self, xin.shape[2], xin.shape[3], False, xin.device, wgrad=True),
@@ -606,17 +597,16 @@ class Engine:
             return op.expanded.pack(weights, transposed, out=old)
         return ops.conv_pack(op.spec, weights, transposed, scale, out=old, order=ops.gemm_order(op.spec, transposed))
 
-    def winograd_filter(self, op, transposed, scale=None, points=16):
-        """Transformed filter (16 packed point matrices; points = 36: the F(4x4,3x3) form) of a conv routed to the Winograd path:
-        cached like `packed`, on the same key -- rebuilt when the weights or the folded scale change, so a teacher's stays put
-        between EMA updates.  The two forms have slots of their own (a layer may run both, on maps of different sizes)."""
-        slot = (id(op), transposed, "winograd") if points == 16 else (id(op), transposed, "winograd", points)
-        return self._cached(self._packs, slot, _pack_key(op, scale), self._build_winograd_filter, op, transposed, scale, points)
+    def winograd_filter(self, op, transposed, scale, form):
+        """Transformed filter (the packed point matrices of `form`, ops.F2 or ops.F4) of a conv routed to the Winograd path: cached
+        like `packed`, on the same key -- rebuilt when the weights or the folded scale change, so a teacher's stays put between EMA
+        updates.  The two forms have slots of their own (a layer may run both, on maps of different sizes)."""
+        return self._cached(self._packs, (id(op), transposed, form.name), _pack_key(op, scale), self._build_winograd_filter, op, transposed,
+                            scale, form)
 
     @staticmethod
-    def _build_winograd_filter(old, op, transposed, scale, points):
-        build = ops.winograd_filter if points == 16 else ops.winograd4_filter
-        return build(op.spec, op.convs[0].weight.detach(), transposed, scale, out=old)
+    def _build_winograd_filter(old, op, transposed, scale, form):
+        return form.filter(op.spec, op.convs[0].weight.detach(), transposed, scale, out=old)
 
     def largest_tensor_bytes(self, Nb, H, W):
         """Bytes of the largest activation (or expanded-conv intermediate) a pass over an [Nb, *, H, W] input creates.  The conv

@@ -315,7 +315,8 @@ def conv_dgrad(spec, dz, weights, in_hw, scale=None, res=None, mask=None, table=
 
 
 # ----------------------------------------------------------------------------------------------
-# Winograd F(2x2,3x3) for the wide dilated 3x3 convolutions (include/dasac_hip.h: dasac_winograd_*)
+# Winograd F(2x2,3x3) and F(4x4,3x3) for the wide dilated 3x3 convolutions (include/dasac_hip.h: dasac_winograd_*, dasac_winograd4_*):
+# ONE implementation of each operation (WinogradForm), the two forms as data (F2, F4), and per form the public names bound to it
 # ----------------------------------------------------------------------------------------------
 # Algorithm of the forward / data-gradient / weight-gradient GEMMs of an eligible convolution:
 #   "auto"    Winograd F(4x4,3x3) where `winograd4_routed` says so (on large maps layer4's conv2 data gradient and no-grad forward, layer3's no-grad forward), else
@@ -346,28 +347,6 @@ def winograd_ok(spec, transposed=False):
     return kh == 3 and kw == 3 and d >= 1 and p == d and C % 16 == 0
 
 
-def winograd_routed(spec, transposed, Nb, H, W):
-    """The routing rule of the engine: eligible, wide enough to pay, the transformed tensors inside the 4 GiB window."""
-    if ALGORITHM != "auto" or not winograd_ok(spec, transposed) or spec.cin * spec.cout < WINOGRAD_MIN_CHANNEL_PRODUCT:
-        return False
-    T = L.load().dasac_winograd_tiles(Nb, H, W, spec.branches[0][2])
-    return T > 0 and 64 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES
-
-
-def winograd_filter(spec, weight, transposed, scale=None, out=None):
-    """U [16, Kpad, Mpad]: the 16 point matrices G g G^T of `weight` [Cout,Cin,3,3] (scale[co] folded in), each packed as
-    `conv_pack` packs a 1x1 convolution; transposed: rotated filter, channels swapped (the data gradient)."""
-    lib = L.load()
-    L.require_gpu(weight, scale)
-    M, K = (spec.cin, spec.cout) if transposed else (spec.cout, spec.cin)
-    shape = (16, lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M))
-    if out is None or tuple(out.shape) != shape:
-        out = torch.empty(shape, dtype=torch.float32, device=weight.device)
-    L.check(lib.dasac_winograd_filter(_c(weight).data_ptr(), L.ptr(scale), spec.cout, spec.cin, int(transposed), out.data_ptr(),
-                                      L.stream_ptr()), "dasac_winograd_filter")
-    return out
-
-
 _wino_tables = {}
 
 
@@ -382,72 +361,158 @@ def _winograd_table(C, T, device):
     return t
 
 
-def winograd_output(y, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
-    """out [Nb,M,H,W] = epilogue(A^T Y A) of the point GEMMs' results y [16, M, T]: + shift, ReLU, ReLU pattern recorded into
-    `bits_out` or the elements whose bit in `mask_bits` is clear zeroed (both ReluBits of out's shape)."""
-    lib = L.load()
-    L.require_gpu(y, out, shift)
-    Nb, M, H, W = out.shape
-    assert y.is_contiguous() and out.is_contiguous() and y.dtype == torch.float32
-    for b in (mask_bits, bits_out):
-        assert b is None or b.shape == tuple(out.shape)
-    with PROFILE.span("winograd_output", 0.0, None, 4.0 * (y.numel() + out.numel())):
-        L.check(lib.dasac_winograd_output(y.data_ptr(), y.numel() * 4, Nb, M, H, W, int(dilation), L.ptr(shift), int(relu),
-                                          0 if mask_bits is None else mask_bits.words.data_ptr(),
-                                          0 if bits_out is None else bits_out.words.data_ptr(), out.data_ptr(), L.stream_ptr()),
-                "dasac_winograd_output")
-    return out
+class WinogradForm:
+    """One form F(tile x tile, 3x3) of the Winograd path: what tells the forms apart as data, the operations written once.
+    name: stem of the C entry points (dasac_<name>_*), of the PROFILE span names and of the error texts.  points: (tile + 2)^2
+    entries of the batched point GEMMs / contractions.  multi_launch: narrow outputs (padded M no multiple of 128, no batched
+    point GEMM) fall back to one `conv_gemm` launch per point -- F(2x2) keeps that form, F(4x4) has none.
+    F(2x2): 16 point products per 2x2 outputs, 2.25 x fewer than direct.  F(4x4) (evaluation points 0, 1, -1, 2, -1/2, inf): 36 per
+    4x4 outputs, 1.71 x fewer again, transformed tensors of 0.59 times the size, at 2 - 4 x the direct kernel's rounding error
+    against float64 (tests/test_gpu_winograd4_conv.py prints the ratio); its tile count is padded to a multiple of 4 with zero tiles."""
+
+    def __init__(self, name, tile, multi_launch):
+        self.name, self.tile, self.points, self.multi_launch = name, tile, (tile + 2) ** 2, multi_launch
+        self.sum_entry = tile + 3       # point (1,1), evaluation point 1 on both axes: its row of A is all ones, its row sums are the channel sums of dz
+
+    def entry(self, fn):
+        return getattr(L.load(), "dasac_{}_{}".format(self.name, fn))
+
+    def tiles(self, Nb, H, W, dilation):
+        """T, the pixel axis of the transformed tensors [points, C, T]; 0: more than 2^30 tiles."""
+        return self.entry("tiles")(Nb, H, W, int(dilation))
+
+    def fits(self, C, M, T):
+        """The transformed tensors [points, C or M, T] lie inside the 4 GiB window of the kernels' buffer descriptors."""
+        return T > 0 and 4 * self.points * max(C, M) * T <= _MAX_TENSOR_BYTES
+
+    def filter(self, spec, weight, transposed, scale=None, out=None):
+        """U [points, Kpad, Mpad]: the point matrices G g G^T of `weight` [Cout,Cin,3,3] (scale[co] folded in), each packed as
+        `conv_pack` packs a 1x1 convolution; transposed: rotated filter, channels swapped (the data gradient)."""
+        lib = L.load()
+        L.require_gpu(weight, scale)
+        M, K = (spec.cin, spec.cout) if transposed else (spec.cout, spec.cin)
+        shape = (self.points, lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M))
+        if out is None or tuple(out.shape) != shape:
+            out = torch.empty(shape, dtype=torch.float32, device=weight.device)
+        L.check(self.entry("filter")(_c(weight).data_ptr(), L.ptr(scale), spec.cout, spec.cin, int(transposed), out.data_ptr(), L.stream_ptr()),
+                "dasac_{}_filter".format(self.name))
+        return out
+
+    def output(self, y, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
+        """out [Nb,M,H,W] = epilogue(A^T Y A) of the point GEMMs' results y [points, M, T]: + shift, ReLU, ReLU pattern recorded into
+        `bits_out` or the elements whose bit in `mask_bits` is clear zeroed (both ReluBits of out's shape)."""
+        L.require_gpu(y, out, shift)
+        Nb, M, H, W = out.shape
+        assert y.is_contiguous() and out.is_contiguous() and y.dtype == torch.float32
+        for b in (mask_bits, bits_out):
+            assert b is None or b.shape == tuple(out.shape)
+        with PROFILE.span(self.name + "_output", 0.0, None, 4.0 * (y.numel() + out.numel())):
+            L.check(self.entry("output")(y.data_ptr(), y.numel() * 4, Nb, M, H, W, int(dilation), L.ptr(shift), int(relu),
+                                      0 if mask_bits is None else mask_bits.words.data_ptr(),
+                                      0 if bits_out is None else bits_out.words.data_ptr(), out.data_ptr(), L.stream_ptr()),
+                    "dasac_{}_output".format(self.name))
+        return out
+
+    def conv(self, x, u, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None, gemm_schedule="auto"):
+        """out [Nb,M,H,W] = epilogue(conv3x3(x [Nb,C,H,W], dilation = padding)) with the transformed filter u = `filter`
+        (forward, or the data-gradient form with x = dz): input transform, the point GEMMs, output transform.
+        The two transformed tensors [points, C, T] and [points, M, T] live in the stream's scratch buffer.
+        gemm_schedule: "auto" issues the point GEMMs as ONE batched launch (`conv_gemm_batched`: a single point's tiles -- layer4:
+        604 on 1024 resident slots -- never fill the chip, all points make whole rounds; it exists for padded M a multiple of 128);
+        a `multi_launch` form runs narrower outputs as None, and takes 1 / 2 / None to issue one `conv_gemm` launch per point on that
+        schedule (one block per tile -- bit-equal to the batched launch --, stream-K, the library's choice; tools/winograd_ab.py)."""
+        lib = L.load()
+        L.require_gpu(x, u, out)
+        P = self.points
+        Nb, C, H, W = x.shape
+        M = out.shape[1]
+        assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (Nb, M, H, W)
+        assert tuple(u.shape) == (P, lib.dasac_conv_kpad(C), lib.dasac_conv_mpad(M)) and u.is_contiguous()
+        if gemm_schedule == "auto" and lib.dasac_conv_mpad(M) % 128 != 0:
+            gemm_schedule = None       # narrow outputs (the batched launch exists for the 128-row tile only): P launches, the library's choice
+        if gemm_schedule != "auto" and not self.multi_launch:
+            raise L.DasacError("{}_conv: {} output channels have no batched point GEMM".format(self.name, M))
+        T = self.tiles(Nb, H, W, dilation)
+        if not self.fits(C, M, T):
+            raise L.DasacError("{}_conv: [{}, {}, tiles] exceeds the 4 GiB buffer-descriptor window".format(self.name, P, max(C, M)))
+        v_elems, y_elems = P * C * T, P * M * T
+        ws = L.workspace(4 * (v_elems + y_elems), x.device)[:4 * (v_elems + y_elems)].view(torch.float32)
+        v, y = ws[:v_elems].view(P, C, T), ws[v_elems:v_elems + y_elems].view(P, M, T)
+        with PROFILE.span(self.name + "_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
+            L.check(self.entry("input")(x.data_ptr(), Nb, C, H, W, int(dilation), v.data_ptr(), v_elems * 4, L.stream_ptr()),
+                    "dasac_{}_input".format(self.name))
+        table = _winograd_table(C, T, x.device)
+        if gemm_schedule == "auto":
+            conv_gemm_batched(v.view(P, 1, C, 1, T), u, table, y.view(P, 1, M, 1, T), (1, T), 1, M, C)
+        else:
+            for pt in range(P):
+                conv_gemm(v[pt].view(1, C, 1, T), u[pt], table, y[pt].view(1, M, 1, T), (1, T), 1, M, C, schedule=gemm_schedule)
+        return self.output(y, out, dilation, shift, relu, mask_bits, bits_out)
+
+    def wgrad(self, spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=None):
+        """dW [Cout,Cin,3,3] of an eligible 3x3 convolution as G^T [sum over tiles (A dY A^T) (.) (B^T x B)] G: the input transform of
+        x, its adjoint on dz, ONE batched launch of the point contractions over pixel splits, and a finish that adds the splits in a
+        fixed order, transforms back and multiplies by scale[co].  `dot` [dot_rows(spec), Cout], `sum_dz` [Cout] and `out` are those
+        of `conv_wgrad`.  The two transformed tensors and the slabs live in the stream's scratch buffer."""
+        lib = L.load()
+        L.require_gpu(dz, x, weight, scale, dot, sum_dz)
+        P, name = self.points, self.name
+        Nb, C, H, W = x.shape
+        M, d = dz.shape[1], int(spec.branches[0][2])
+        assert winograd_ok(spec) and (C, M) == (spec.cin, spec.cout) and tuple(dz.shape) == (Nb, M, H, W) and x.is_contiguous()
+        assert dot is None or (tuple(dot.shape) == (dot_rows(spec), M) and dot.is_contiguous())
+        T = self.tiles(Nb, H, W, d)
+        slab_bytes = lib.dasac_conv_wgrad_batched_workspace(P, M, C, T) if T > 0 else 0
+        if slab_bytes == 0 or not self.fits(C, M, T):
+            raise L.DasacError("{}_wgrad: {} x {} channels over {} tiles has no batched point contraction".format(name, M, C, T))
+        v_elems, m_elems = P * C * T, P * M * T
+        ws = L.workspace(4 * (v_elems + m_elems) + slab_bytes, x.device)
+        v, dm, slabs = ws[:4 * v_elems], ws[4 * v_elems:4 * (v_elems + m_elems)], ws[4 * (v_elems + m_elems):]
+        dz = _c(dz)
+        with PROFILE.span(name + "_wgrad_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
+            L.check(self.entry("input")(x.data_ptr(), Nb, C, H, W, d, v.data_ptr(), v.numel(), L.stream_ptr()), "dasac_{}_input".format(name))
+        with PROFILE.span(name + "_wgrad_grad", 0.0, None, 4.0 * (dz.numel() + m_elems)):
+            L.check(self.entry("grad_input")(dz.data_ptr(), Nb, M, H, W, d, dm.data_ptr(), dm.numel(), L.stream_ptr()),
+                    "dasac_{}_grad_input".format(name))
+        with PROFILE.span(name + "_wgrad_gemm", 2.0 * P * M * C * T, (M, C, T, 1, 1, False, False), 4.0 * (v_elems + m_elems + P * M * C)):
+            L.check(lib.dasac_conv_wgrad_batched(dm.data_ptr(), v.data_ptr(), P, M, C, T, M * T, C * T, self.sum_entry, slabs.data_ptr(),
+                                                 slabs.numel(), L.stream_ptr()), "dasac_conv_wgrad_batched")
+        dw = _dest(out, weight)
+        with PROFILE.span(name + "_wgrad_finish", 0.0, None, float(slab_bytes) + 8.0 * weight.numel()):
+            L.check(self.entry("wgrad_finish")(slabs.data_ptr(), slabs.numel(), M, C, T, _c(weight).data_ptr(), L.ptr(scale), dw.data_ptr(),
+                                            L.ptr(dot), L.ptr(sum_dz), L.stream_ptr()), "dasac_{}_wgrad_finish".format(name))
+        return dw
 
 
-def winograd_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None, gemm_schedule="auto"):
-    """out [Nb,M,H,W] = epilogue(conv3x3(x [Nb,C,H,W], dilation = padding)) with the transformed filter u = `winograd_filter`
-    (forward, or the data-gradient form with x = dz): input transform, the 16 point GEMMs, output transform.
-    The two transformed tensors [16, C, T] and [16, M, T] live in the stream's scratch buffer.
-    gemm_schedule: "auto" issues the 16 point GEMMs as ONE batched launch (`conv_gemm_batched`: a single point's tiles -- layer4:
-    604 on 1024 resident slots -- never fill the chip, 16 points make whole rounds; M <= 64 has no batched form and runs as None);
-    1 / 2 / None issue 16 `conv_gemm` launches on that schedule (one block per tile -- bit-equal to the batched launch --, stream-K,
-    the library's choice; tools/winograd_ab.py)."""
-    lib = L.load()
-    L.require_gpu(x, u, out)
-    Nb, C, H, W = x.shape
-    M = out.shape[1]
-    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (Nb, M, H, W)
-    assert tuple(u.shape) == (16, lib.dasac_conv_kpad(C), lib.dasac_conv_mpad(M)) and u.is_contiguous()
-    T = lib.dasac_winograd_tiles(Nb, H, W, int(dilation))
-    if T <= 0 or 64 * max(C, M) * T > _MAX_TENSOR_BYTES:
-        raise L.DasacError("winograd_conv: [16, {}, tiles] exceeds the 4 GiB buffer-descriptor window".format(max(C, M)))
-    v_elems, y_elems = 16 * C * T, 16 * M * T
-    ws = L.workspace(4 * (v_elems + y_elems), x.device)[:4 * (v_elems + y_elems)].view(torch.float32)
-    v, y = ws[:v_elems].view(16, C, T), ws[v_elems:v_elems + y_elems].view(16, M, T)
-    with PROFILE.span("winograd_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
-        L.check(lib.dasac_winograd_input(x.data_ptr(), Nb, C, H, W, int(dilation), v.data_ptr(), v_elems * 4, L.stream_ptr()),
-                "dasac_winograd_input")
-    table = _winograd_table(C, T, x.device)
-    if gemm_schedule == "auto" and lib.dasac_conv_mpad(M) % 128 != 0:
-        gemm_schedule = None       # narrow outputs (the batched launch exists for the 128-row tile only): 16 launches, the library's choice
-    if gemm_schedule == "auto":
-        conv_gemm_batched(v.view(16, 1, C, 1, T), u, table, y.view(16, 1, M, 1, T), (1, T), 1, M, C)
-    else:
-        for pt in range(16):
-            conv_gemm(v[pt].view(1, C, 1, T), u[pt], table, y[pt].view(1, M, 1, T), (1, T), 1, M, C, schedule=gemm_schedule)
-    return winograd_output(y, out, dilation, shift, relu, mask_bits, bits_out)
+F2 = WinogradForm("winograd", 2, multi_launch=True)
+F4 = WinogradForm("winograd4", 4, multi_launch=False)
+winograd_filter, winograd_output, winograd_conv, winograd_wgrad = F2.filter, F2.output, F2.conv, F2.wgrad
+winograd4_filter, winograd4_output, winograd4_conv, winograd4_wgrad = F4.filter, F4.output, F4.conv, F4.wgrad
 
 
-# The same forward / data gradient as F(4x4,3x3) (the weight gradient's evaluation points, so `dasac_winograd4_input` serves x, dz and
-# the weight gradient alike): 36 point products per 16 outputs against 64, transformed tensors of 0.59 times the size, at 2 - 4 x the
-# direct kernel's rounding error against float64 (tests/test_gpu_winograd4_conv.py prints the ratio).  Routed per
-# (Cin, Cout, dilation, data gradient?, grad-enabled pass?) where the per-conv gain AND the end-to-end accuracy bounds of
-# tests/test_gpu_fullres.py were measured to hold (profiles/winograd4_conv_ab.txt, profiles/EXPERIMENTS.md); anything else keeps
-# F(2x2) or the direct GEMM.  Layer3's 256 -> 256 is routed in no-grad forwards only (the teacher, inference): a grad-enabled pass
-# keeps the direct launches tests/test_gpu_fullres.py counts.  Layer4's forward is routed in no-grad passes only as well: in a
-# grad-enabled pass its 4 x larger difference to the direct kernel flips more ReLUs that sit at zero, each of which moves a gradient
-# row by about 1e-2 of its maximum, and tests/test_gpu_winograd4_wgrad.py (512 planes at 2 x 33 x 33, auto against direct, bound 1e-3)
-# measured 1.6e-2 with it and 3.8e-6 without.  VGG16's undilated 512 -> 512 layers were not measured, so the table carries the dilation.
+# ---- routing: policy, one rule per form and GEMM, each from its own measurements ---------------------------------------------------
+def winograd_routed(spec, transposed, Nb, H, W):
+    """The engine's rule for the F(2x2,3x3) forward (transposed: data gradient): eligible, wide enough to pay, the transformed
+    tensors inside the 4 GiB window."""
+    if ALGORITHM != "auto" or not winograd_ok(spec, transposed) or spec.cin * spec.cout < WINOGRAD_MIN_CHANNEL_PRODUCT:
+        return False
+    return F2.fits(spec.cin, spec.cout, F2.tiles(Nb, H, W, spec.branches[0][2]))
+
+
+# The forward / data gradient as F(4x4,3x3) is routed per (Cin, Cout, dilation, data gradient?, grad-enabled pass?) where the per-conv
+# gain AND the end-to-end accuracy bounds of tests/test_gpu_fullres.py were measured to hold (profiles/winograd4_conv_ab.txt,
+# profiles/EXPERIMENTS.md); anything else keeps F(2x2) or the direct GEMM.  Layer3's 256 -> 256 is routed in no-grad forwards only
+# (the teacher, inference): a grad-enabled pass keeps the direct launches tests/test_gpu_fullres.py counts.  Layer4's forward is
+# routed in no-grad passes only as well: in a grad-enabled pass its 4 x larger difference to the direct kernel flips more ReLUs that
+# sit at zero, each of which moves a gradient row by about 1e-2 of its maximum, and tests/test_gpu_winograd4_wgrad.py (512 planes at
+# 2 x 33 x 33, auto against direct, bound 1e-3) measured 1.6e-2 with it and 3.8e-6 without.  VGG16's undilated 512 -> 512 layers were
+# not measured, so the table carries the dilation.
 WINOGRAD4_ROUTES = {
     (512, 512, 4, True, True),       # (a) layer4 conv2, data gradient
     (512, 512, 4, False, False),     # (b) layer4 conv2, forward of a no-grad pass (of a grad-enabled pass: not routed, see above)
     (256, 256, 2, False, False),     # (c) layer3 conv2, no-grad forward
 }
+WINOGRAD4_MIN_SAMPLES = 8                    # per phase and axis: two whole four-output tiles; below that most of a tile is overhang
 
 
 def winograd4_routed(spec, transposed, Nb, H, W, grad):
@@ -460,128 +525,37 @@ def winograd4_routed(spec, transposed, Nb, H, W, grad):
     d = spec.branches[0][2]
     if (spec.cin, spec.cout, d, bool(transposed), bool(grad)) not in WINOGRAD4_ROUTES:
         return False
-    lib = L.load()
-    if lib.dasac_conv_mpad(spec.cin if transposed else spec.cout) % 128:
+    if L.load().dasac_conv_mpad(spec.cin if transposed else spec.cout) % 128:
         return False
     if H // d < WINOGRAD4_MIN_SAMPLES or W // d < WINOGRAD4_MIN_SAMPLES:
         return False
-    T = lib.dasac_winograd4_tiles(Nb, H, W, d)
-    return T > 0 and 144 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES
+    return F4.fits(spec.cin, spec.cout, F4.tiles(Nb, H, W, d))
 
 
-def winograd4_filter(spec, weight, transposed, scale=None, out=None):
-    """U [36, Kpad, Mpad]: `winograd_filter` in the F(4x4,3x3) form, the 36 point matrices G g G^T with the 6x3 G."""
-    lib = L.load()
-    L.require_gpu(weight, scale)
-    M, K = (spec.cin, spec.cout) if transposed else (spec.cout, spec.cin)
-    shape = (36, lib.dasac_conv_kpad(K), lib.dasac_conv_mpad(M))
-    if out is None or tuple(out.shape) != shape:
-        out = torch.empty(shape, dtype=torch.float32, device=weight.device)
-    L.check(lib.dasac_winograd4_filter(_c(weight).data_ptr(), L.ptr(scale), spec.cout, spec.cin, int(transposed), out.data_ptr(),
-                                       L.stream_ptr()), "dasac_winograd4_filter")
-    return out
-
-
-def winograd4_output(y, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
-    """out [Nb,M,H,W] = epilogue(A^T Y A) of the point GEMMs' results y [36, M, T]; the epilogue of `winograd_output`."""
-    lib = L.load()
-    L.require_gpu(y, out, shift)
-    Nb, M, H, W = out.shape
-    assert y.is_contiguous() and out.is_contiguous() and y.dtype == torch.float32
-    for b in (mask_bits, bits_out):
-        assert b is None or b.shape == tuple(out.shape)
-    with PROFILE.span("winograd4_output", 0.0, None, 4.0 * (y.numel() + out.numel())):
-        L.check(lib.dasac_winograd4_output(y.data_ptr(), y.numel() * 4, Nb, M, H, W, int(dilation), L.ptr(shift), int(relu),
-                                           0 if mask_bits is None else mask_bits.words.data_ptr(),
-                                           0 if bits_out is None else bits_out.words.data_ptr(), out.data_ptr(), L.stream_ptr()),
-                "dasac_winograd4_output")
-    return out
-
-
-def winograd4_conv(x, u, out, dilation, shift=None, relu=False, mask_bits=None, bits_out=None):
-    """`winograd_conv` in the F(4x4,3x3) form with u = `winograd4_filter`: the 6x6-patch input transform, ONE batched launch of the
-    36 point GEMMs (M padded to a multiple of 128 only), the output transform.  V [36, C, T] and Y [36, M, T] live in the stream's
-    scratch buffer; T counts the tiles rounded up to a multiple of 4, the padding tiles zero in V and never read from Y."""
-    lib = L.load()
-    L.require_gpu(x, u, out)
-    Nb, C, H, W = x.shape
-    M = out.shape[1]
-    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (Nb, M, H, W)
-    assert tuple(u.shape) == (36, lib.dasac_conv_kpad(C), lib.dasac_conv_mpad(M)) and u.is_contiguous()
-    if lib.dasac_conv_mpad(M) % 128 != 0:
-        raise L.DasacError("winograd4_conv: {} output channels have no batched point GEMM".format(M))
-    T = lib.dasac_winograd4_tiles(Nb, H, W, int(dilation))
-    if T <= 0 or 144 * max(C, M) * T > _MAX_TENSOR_BYTES:
-        raise L.DasacError("winograd4_conv: [36, {}, tiles] exceeds the 4 GiB buffer-descriptor window".format(max(C, M)))
-    v_elems, y_elems = 36 * C * T, 36 * M * T
-    ws = L.workspace(4 * (v_elems + y_elems), x.device)[:4 * (v_elems + y_elems)].view(torch.float32)
-    v, y = ws[:v_elems].view(36, C, T), ws[v_elems:v_elems + y_elems].view(36, M, T)
-    with PROFILE.span("winograd4_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
-        L.check(lib.dasac_winograd4_input(x.data_ptr(), Nb, C, H, W, int(dilation), v.data_ptr(), v_elems * 4, L.stream_ptr()),
-                "dasac_winograd4_input")
-    conv_gemm_batched(v.view(36, 1, C, 1, T), u, _winograd_table(C, T, x.device), y.view(36, 1, M, 1, T), (1, T), 1, M, C)
-    return winograd4_output(y, out, dilation, shift, relu, mask_bits, bits_out)
+def winograd_form(spec, transposed, Nb, H, W, grad):
+    """The form the engine runs the forward (transposed: data gradient) GEMM of `spec` in: F4, F2, or None for the direct GEMM."""
+    if winograd4_routed(spec, transposed, Nb, H, W, grad):
+        return F4
+    return F2 if winograd_routed(spec, transposed, Nb, H, W) else None
 
 
 # The weight gradient of the same convolutions has its own threshold: it is routed where it measured faster on its own, whatever the
 # forward and the data gradient of the layer do -- layer4's 512 -> 512 (2.80 -> 1.64 ms per conv) AND layer3's 256 -> 256 (0.714 ->
 # 0.520 ms; profiles/winograd_wgrad_ab.txt): no test counts conv_wgrad launches.
 WINOGRAD_WGRAD_MIN_CHANNEL_PRODUCT = 256 * 256
+# As F(4x4) -- a few times the rounding error, which a weight gradient, a terminal sum, takes everywhere -- it is routed per layer where
+# it measured faster than the F(2x2) form on its own (profiles/winograd4_wgrad_ab.txt): a (Cin, Cout) pair missing here stays F(2x2).
+WINOGRAD4_WGRAD_LAYERS = {(256, 256), (512, 512)}
 
 
 def winograd_wgrad_routed(spec, Nb, H, W):
-    """The engine's rule for the weight gradient: eligible (`winograd_ok`: one 3x3 branch, fp32, ...), wide enough to pay, the
-    transformed tensors inside the 4 GiB window and a shape the batched point contraction takes (channel counts multiples of
+    """The engine's rule for the F(2x2,3x3) weight gradient: eligible (`winograd_ok`: one 3x3 branch, fp32, ...), wide enough to pay,
+    the transformed tensors inside the 4 GiB window and a shape the batched point contraction takes (channel counts multiples of
     128, a tile count that is a multiple of 4: dasac_conv_wgrad_batched)."""
     if ALGORITHM != "auto" or not winograd_ok(spec) or spec.cin * spec.cout < WINOGRAD_WGRAD_MIN_CHANNEL_PRODUCT:
         return False
-    lib = L.load()
-    T = lib.dasac_winograd_tiles(Nb, H, W, spec.branches[0][2])
-    return T > 0 and 64 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES \
-        and lib.dasac_conv_wgrad_batched_splits(16, spec.cout, spec.cin, T) > 0
-
-
-def winograd_wgrad(spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=None):
-    """dW [Cout,Cin,3,3] of an eligible 3x3 convolution as G^T [sum over tiles (A dY A^T) (.) (B^T x B)] G: the input transform of
-    x, its adjoint on dz, ONE batched launch of the 16 point contractions over pixel splits, and a finish that adds the splits in a
-    fixed order, transforms back and multiplies by scale[co].  `dot` [dot_rows(spec), Cout], `sum_dz` [Cout] and `out` are those
-    of `conv_wgrad`.  The two transformed tensors and the slabs live in the stream's scratch buffer."""
-    lib = L.load()
-    L.require_gpu(dz, x, weight, scale, dot, sum_dz)
-    Nb, C, H, W = x.shape
-    M, d = dz.shape[1], int(spec.branches[0][2])
-    assert winograd_ok(spec) and (C, M) == (spec.cin, spec.cout) and tuple(dz.shape) == (Nb, M, H, W) and x.is_contiguous()
-    assert dot is None or (tuple(dot.shape) == (dot_rows(spec), M) and dot.is_contiguous())
-    T = lib.dasac_winograd_tiles(Nb, H, W, d)
-    slab_bytes = lib.dasac_conv_wgrad_batched_workspace(16, M, C, T) if T > 0 else 0
-    if slab_bytes == 0 or 64 * max(C, M) * T > _MAX_TENSOR_BYTES:
-        raise L.DasacError("winograd_wgrad: {} x {} channels over {} tiles has no batched point contraction".format(M, C, T))
-    v_elems, m_elems = 16 * C * T, 16 * M * T
-    ws = L.workspace(4 * (v_elems + m_elems) + slab_bytes, x.device)
-    v, dm, slabs = ws[:4 * v_elems], ws[4 * v_elems:4 * (v_elems + m_elems)], ws[4 * (v_elems + m_elems):]
-    dz = _c(dz)
-    with PROFILE.span("winograd_wgrad_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
-        L.check(lib.dasac_winograd_input(x.data_ptr(), Nb, C, H, W, d, v.data_ptr(), v.numel(), L.stream_ptr()), "dasac_winograd_input")
-    with PROFILE.span("winograd_wgrad_grad", 0.0, None, 4.0 * (dz.numel() + m_elems)):
-        L.check(lib.dasac_winograd_grad_input(dz.data_ptr(), Nb, M, H, W, d, dm.data_ptr(), dm.numel(), L.stream_ptr()),
-                "dasac_winograd_grad_input")
-    with PROFILE.span("winograd_wgrad_gemm", 2.0 * 16 * M * C * T, (M, C, T, 1, 1, False, False), 4.0 * (v_elems + m_elems + 16 * M * C)):
-        # entry 5 = point (1,1): its row sums are the channel sums of dz
-        L.check(lib.dasac_conv_wgrad_batched(dm.data_ptr(), v.data_ptr(), 16, M, C, T, M * T, C * T, 5, slabs.data_ptr(), slabs.numel(),
-                                             L.stream_ptr()), "dasac_conv_wgrad_batched")
-    dw = _dest(out, weight)
-    with PROFILE.span("winograd_wgrad_finish", 0.0, None, float(slab_bytes) + 8.0 * weight.numel()):
-        L.check(lib.dasac_winograd_wgrad_finish(slabs.data_ptr(), slabs.numel(), M, C, T, _c(weight).data_ptr(), L.ptr(scale), dw.data_ptr(),
-                                                L.ptr(dot), L.ptr(sum_dz), L.stream_ptr()), "dasac_winograd_wgrad_finish")
-    return dw
-
-
-# The same weight gradient as F(4x4,3x3) (evaluation points 0, 1, -1, 2, -1/2, inf): 36 point products per 4x4-output tile against
-# 4 x 16, and transformed tensors of 0.59 times the size, at a few times the rounding error -- which a weight gradient, a terminal
-# sum, takes everywhere; the forward and the data gradient take it per measured route (WINOGRAD4_ROUTES above).  Routed per layer where it
-# measured faster than the F(2x2) form on its own (profiles/winograd4_wgrad_ab.txt): a (Cin, Cout) pair missing here stays F(2x2).
-WINOGRAD4_WGRAD_LAYERS = {(256, 256), (512, 512)}
-WINOGRAD4_MIN_SAMPLES = 8                    # per phase and axis: two whole four-output tiles; below that most of a tile is overhang
+    T = F2.tiles(Nb, H, W, spec.branches[0][2])
+    return F2.fits(spec.cin, spec.cout, T) and L.load().dasac_conv_wgrad_batched_splits(F2.points, spec.cout, spec.cin, T) > 0
 
 
 def winograd4_wgrad_routed(spec, Nb, H, W):
@@ -594,45 +568,15 @@ def winograd4_wgrad_routed(spec, Nb, H, W):
     d = spec.branches[0][2]
     if H // d < WINOGRAD4_MIN_SAMPLES or W // d < WINOGRAD4_MIN_SAMPLES:
         return False
-    lib = L.load()
-    T = lib.dasac_winograd4_tiles(Nb, H, W, d)
-    return T > 0 and 144 * max(spec.cin, spec.cout) * T <= _MAX_TENSOR_BYTES \
-        and lib.dasac_conv_wgrad_batched_splits(36, spec.cout, spec.cin, T) > 0
+    T = F4.tiles(Nb, H, W, d)
+    return F4.fits(spec.cin, spec.cout, T) and L.load().dasac_conv_wgrad_batched_splits(F4.points, spec.cout, spec.cin, T) > 0
 
 
-def winograd4_wgrad(spec, dz, x, weight, scale=None, dot=None, sum_dz=None, out=None):
-    """`winograd_wgrad` in the F(4x4,3x3) form: the 6x6-patch input transform of x, A dY A^T of every tile's 4x4 output pixels,
-    ONE batched launch of the 36 point contractions, and the finish (splits added in a fixed order, G^T (.) G from 6x6 to 3x3,
-    scale[co], `dot` and `sum_dz` as `conv_wgrad` leaves them).  The tile count is padded to a multiple of 4 with zero tiles, so
-    any batch and map size is taken."""
-    lib = L.load()
-    L.require_gpu(dz, x, weight, scale, dot, sum_dz)
-    Nb, C, H, W = x.shape
-    M, d = dz.shape[1], int(spec.branches[0][2])
-    assert winograd_ok(spec) and (C, M) == (spec.cin, spec.cout) and tuple(dz.shape) == (Nb, M, H, W) and x.is_contiguous()
-    assert dot is None or (tuple(dot.shape) == (dot_rows(spec), M) and dot.is_contiguous())
-    T = lib.dasac_winograd4_tiles(Nb, H, W, d)
-    slab_bytes = lib.dasac_conv_wgrad_batched_workspace(36, M, C, T) if T > 0 else 0
-    if slab_bytes == 0 or 144 * max(C, M) * T > _MAX_TENSOR_BYTES:
-        raise L.DasacError("winograd4_wgrad: {} x {} channels over {} tiles has no batched point contraction".format(M, C, T))
-    v_elems, m_elems = 36 * C * T, 36 * M * T
-    ws = L.workspace(4 * (v_elems + m_elems) + slab_bytes, x.device)
-    v, dm, slabs = ws[:4 * v_elems], ws[4 * v_elems:4 * (v_elems + m_elems)], ws[4 * (v_elems + m_elems):]
-    dz = _c(dz)
-    with PROFILE.span("winograd4_wgrad_input", 0.0, None, 4.0 * (x.numel() + v_elems)):
-        L.check(lib.dasac_winograd4_input(x.data_ptr(), Nb, C, H, W, d, v.data_ptr(), v.numel(), L.stream_ptr()), "dasac_winograd4_input")
-    with PROFILE.span("winograd4_wgrad_grad", 0.0, None, 4.0 * (dz.numel() + m_elems)):
-        L.check(lib.dasac_winograd4_grad_input(dz.data_ptr(), Nb, M, H, W, d, dm.data_ptr(), dm.numel(), L.stream_ptr()),
-                "dasac_winograd4_grad_input")
-    with PROFILE.span("winograd4_wgrad_gemm", 2.0 * 36 * M * C * T, (M, C, T, 1, 1, False, False), 4.0 * (v_elems + m_elems + 36 * M * C)):
-        # entry 7 = point (1,1), evaluation point 1 on both axes: its row sums are the channel sums of dz
-        L.check(lib.dasac_conv_wgrad_batched(dm.data_ptr(), v.data_ptr(), 36, M, C, T, M * T, C * T, 7, slabs.data_ptr(), slabs.numel(),
-                                             L.stream_ptr()), "dasac_conv_wgrad_batched")
-    dw = _dest(out, weight)
-    with PROFILE.span("winograd4_wgrad_finish", 0.0, None, float(slab_bytes) + 8.0 * weight.numel()):
-        L.check(lib.dasac_winograd4_wgrad_finish(slabs.data_ptr(), slabs.numel(), M, C, T, _c(weight).data_ptr(), L.ptr(scale), dw.data_ptr(),
-                                                 L.ptr(dot), L.ptr(sum_dz), L.stream_ptr()), "dasac_winograd4_wgrad_finish")
-    return dw
+def winograd_wgrad_form(spec, Nb, H, W):
+    """The form the engine runs the weight gradient of `spec` in: F4, F2, or None for `conv_wgrad`."""
+    if winograd4_wgrad_routed(spec, Nb, H, W):
+        return F4
+    return F2 if winograd_wgrad_routed(spec, Nb, H, W) else None
 
 
 def dot_rows(spec):

@@ -1,5 +1,5 @@
-"""The kernels of the Winograd F(4x4,3x3) forward and data gradient (filter_transform4, the two instantiations of output_transform4
-and relu_bits_pack of csrc/winograd.hip) use no scratch, no LDS and spill nothing: no private segment, no spill count in the code object
+"""The kernels of the Winograd F(4x4,3x3) forward and data gradient (filter_transform<F4>, the two instantiations of output_transform4
+and relu_bits_pack of csrc/winograd.hip) and filter_transform<F2> use no scratch, no LDS and spill nothing: no private segment, no spill count in the code object
 metadata, no scratch instruction and no SGPR-spill lane move in their bodies.  The method of test_kernel_resources_winograd4.py:
 cross-compiles to gfx950 assembly; no GPU."""
 import os
@@ -10,7 +10,8 @@ import pytest
 
 from test_kernel_resources import HIPCC, _asm, _kernel_meta
 
-KERNELS = {"filter_transform4": 1, "output_transform4": 2, "relu_bits_pack": 1}            # name -> instantiations
+# substring of the mangled name (the form is the template argument) -> instantiations
+KERNELS = {"filter_transformINS0_2F4E": 1, "output_transform4": 2, "relu_bits_pack": 1, "filter_transformINS0_2F2E": 1}
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.isfile(HIPCC), reason="hipcc not available")

@@ -7,7 +7,7 @@ recorded bits) and weight gradient (scaled, with the frozen BN's dot rows and ch
 Per repetition: `iters` back-to-back evaluations between one HIP event pair -> ms per conv, summing every launch that replaces
 the direct one (input transform + the 16 point GEMMs, as one batched launch or as 16 + output transform; weight gradient: both
 transforms + the batched point contraction + finish, against conv_wgrad + its finish).  A second pass splits
-the Winograd time per kernel with an event pair per launch (ops.PROFILE); the weight gradient has a second Winograd leg, F(4x4,3x3)
+the Winograd time per kernel with an event pair per launch (ops.PROFILE; median and max - min of `reps` repetitions); the weight gradient has a second Winograd leg, F(4x4,3x3)
 (ops.winograd4_wgrad), with its own split, and so have the forward and the data gradient (ops.winograd4_conv; the forward also
 without recorded bits, as a no-grad pass runs it).  With DASAC_LIB naming an older build of the library
 the figures are that build's (the A/B against the parent commit on the same box): --direct-only for its direct GEMM,
@@ -107,15 +107,19 @@ def main():
         for name in [n for n in legs if "winograd" in n]:
             legs[name]()
             torch.cuda.synchronize()
-            ops.PROFILE.start()
-            for _ in range(args.iters):
-                legs[name]()
-            prof = ops.PROFILE.stop()
-            print(name + ", per-kernel split (event pair per launch):")
-            for k, v in sorted(prof.items()):
-                print("    {:<28s} {:2d} launches  {:.4f} ms per conv   {:.1f} TFLOP/s  {:.2f} TB/s algorithmic".format(
-                    k, v["launches"] // args.iters, v["seconds"] / args.iters * 1e3, v["flops"] / max(v["seconds"], 1e-12) / 1e12,
-                    v["bytes"] / max(v["seconds"], 1e-12) / 1e12))
+            profs = []
+            for _ in range(args.reps):
+                ops.PROFILE.start()
+                for _ in range(args.iters):
+                    legs[name]()
+                profs.append(ops.PROFILE.stop())
+            print(name + ", per-kernel split (event pair per launch), median of {} repetitions:".format(args.reps))
+            for k, v in sorted(profs[0].items()):
+                ms = sorted(p[k]["seconds"] / args.iters * 1e3 for p in profs)
+                sec = ms[len(ms) // 2] * 1e-3 * args.iters
+                print("    {:<28s} {:2d} launches  {:.4f} ms per conv   spread {:.4f}   {:.1f} TFLOP/s  {:.2f} TB/s algorithmic".format(
+                    k, v["launches"] // args.iters, ms[len(ms) // 2], ms[-1] - ms[0], v["flops"] / max(sec, 1e-12) / 1e12,
+                    v["bytes"] / max(sec, 1e-12) / 1e12))
 
 
 if __name__ == "__main__":

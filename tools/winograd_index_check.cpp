@@ -159,7 +159,7 @@ static void check_shape(int N, int C, int M, int H, int W, int d, bool say = tru
                 touch ? " (arrays touched)" : "");
 }
 
-// ---- F(4x4,3x3): input_transform4 and grad_transform4 of winograd.hip, tensors [36][C][T] with T padded to a multiple of 4 -------
+// ---- F(4x4,3x3): input_transform<F4> and grad_transform<F4> of winograd.hip, tensors [36][C][T] with T padded to a multiple of 4 -------
 static void check_shape4(int N, int C, int M, int H, int W, int d, bool say = true) {
   const Geom g = make_geom<4>(N, H, W, d);
   const int real = N * g.tiles_img;
@@ -226,7 +226,7 @@ static void check_shape4(int N, int C, int M, int H, int W, int d, bool say = tr
       }
     }
   };
-  // ---- input_transform4: 36 gathered taps of the 6x6 patch
+  // ---- input_transform<F4>: 36 gathered taps of the 6x6 patch
   std::vector<int> reads((size_t)N * H * W, 0);
   for (int c : cs)
     for (int tile = 0; tile < g.T; ++tile) {
@@ -250,7 +250,7 @@ static void check_shape4(int N, int C, int M, int H, int W, int d, bool say = tr
     }
   // an input pixel lies in the 6-wide patches (4 apart) of one or two tiles per axis
   for (size_t i = 0; i < reads.size(); ++i) EXPECT(reads[i] >= 1 && reads[i] <= 4, "m=4 pixel %zu read %d times", i, reads[i]);
-  // ---- grad_transform4: the 4x4 output pixels, taps (ey + 1, ex + 1); every pixel of dz exactly once
+  // ---- grad_transform<F4>: the 4x4 output pixels, taps (ey + 1, ex + 1); every pixel of dz exactly once
   std::vector<int> owned((size_t)N * H * W, 0);
   for (int m : ms)
     for (int tile = 0; tile < g.T; ++tile) {
