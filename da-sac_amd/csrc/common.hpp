@@ -47,6 +47,16 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 typedef long long i64x2u __attribute__((ext_vector_type(2), aligned(8)));
 
+// a quad of one fp32 plane: nx = 1..4 pixels from p on, the slots past nx read as 0
+__device__ __forceinline__ f32x4u load_quad(const float* __restrict__ p, int nx) {
+  if (nx == 4) return *reinterpret_cast<const f32x4u*>(p);
+  f32x4u v = f32x4u{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 3; ++e)
+    if (e < nx) v[e] = p[e];
+  return v;
+}
+
 // grid for a grid-stride streaming kernel: enough blocks to fill 256 CUs several times over
 inline int stream_grid(int64_t work_items, int block, int max_blocks = 0) {
   if (max_blocks <= 0) max_blocks = (kNumCu - reserved_cus()) * 16;

@@ -100,16 +100,7 @@ __device__ __forceinline__ void flush_bins(const unsigned int* __restrict__ s, i
   }
 }
 
-// a quad of one fp32 plane: nx = 1..4 pixels from p on, the slots past nx read as 0
-__device__ __forceinline__ f32x4u load_quad(const float* __restrict__ p, int nx) {
-  if (nx == 4) return *reinterpret_cast<const f32x4u*>(p);
-  f32x4u v = f32x4u{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int e = 0; e < 3; ++e)
-    if (e < nx) v[e] = p[e];
-  return v;
-}
-
+// (load_quad of an fp32 plane: common.hpp)
 // four int64 labels; the slots past nx read as `fill`
 __device__ __forceinline__ void load_quad(const int64_t* __restrict__ src, int nx, int64_t fill, int64_t (&g)[4]) {
   if (nx == 4) {

@@ -20,7 +20,7 @@
 // in upsample_softmax, buys that kernel dwordx4 stores of its 76 B per pixel and shared taps at the fixed 8x factor; here the
 // mandatory output is ONE byte per pixel, the sources have S different factors (a scale-0.5 source is upsampled 16x, the
 // full-size one 8x: no common narrow-quad case), and 4 x (19 + 19) live class values would leave two waves per SIMD for a
-// kernel whose time is gathers from L2 and expf, i.e. latency that wants waves (head.hip's round-4 note measured the same
+// kernel whose time is gathers from L2 and expf, i.e. latency that wants waves (upsample.hip's round-4 note measured the same
 // trade going the same way at two pixels per thread).  The source loop is a runtime loop over a by-value argument struct
 // (wave-uniform scalar loads), not unrolled: S x 19 taps in flight would cost the registers that the occupancy needs.
 #include "bilinear.hpp"

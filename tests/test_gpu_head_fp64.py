@@ -1,5 +1,5 @@
-"""The SAC head's loss and view-fusion kernels (csrc/head.hip: ce_loss, ce_bwd_rows / ce_bwd_rows_wave + conf_pixel_sums, warp_affine,
-warp_pool / warp_pool_avg, warp_back) against plain float64 ATen on the CPU, through dasac_hip.ops only.
+"""The SAC head's loss and view-fusion kernels (csrc/cross_entropy.hip: ce_loss, ce_bwd_rows / ce_bwd_rows_wave + conf_pixel_sums;
+csrc/warp.hip: warp_affine, warp_pool / warp_pool_avg, warp_back) against plain float64 ATen on the CPU, through dasac_hip.ops only.
 
 Reference: F.cross_entropy / autograd (through F.interpolate(bilinear, align_corners=True) for the low-resolution gradient),
 F.affine_grid + F.grid_sample(bilinear, zeros, align_corners=False), and the two poolings of sac.py:218-269 written out below,

@@ -1,5 +1,5 @@
 """The element-wise kernels of csrc/pointwise.hip (scale_planes, add2, relu_mask) bit for bit against their one-line torch
-expressions on the CPU, and class_state (csrc/head.hip) against float64 restatements of sac.py:104-117, 120, 151-152, through
+expressions on the CPU, and class_state (csrc/class_prior.hip) against float64 restatements of sac.py:104-117, 120, 151-152, through
 dasac_hip.ops.
 
 scale_planes = x * m[:, :, None, None] (Dropout2d), add = a + b (skip joins; with and without out=, and with out aliasing a as

@@ -1,4 +1,4 @@
-"""The bilinear half of csrc/head.hip -- upsample_softmax<19 | generic, SOFTMAX, NARROW>, q32_to_double, upsample_bwd_x / _y --
+"""The bilinear half of the head, csrc/upsample.hip -- upsample_softmax<19 | generic, SOFTMAX, NARROW>, q32_to_double, upsample_bwd_x / _y --
 against plain float64 ATen on the CPU, through dasac_hip.ops only.
 
 Reference: F.interpolate(x.double(), size, mode="bilinear", align_corners=True), torch.softmax(.., 1) of it times ~ignore, and
@@ -50,7 +50,7 @@ from fp64_yardstick import _ratio, _report
 pytestmark = pytest.mark.gpu
 GSCALE = 0.37
 K_NUM_CU = 256       # common.hpp kNumCu
-K_HB = 256           # head.hip kHB: threads per block of the head's streaming kernels
+K_HB = 256           # head_common.hpp kHB: threads per block of the head's streaming kernels
 
 
 # ---- the launcher, restated ----------------------------------------------------------------------------------------------------
@@ -60,7 +60,7 @@ def _ac_scale(n_in, n_out):
 
 
 def _narrow(w, W):
-    """dasac_upsample_softmax's `narrow` loop (head.hip, "tap_ac's column arithmetic, on the host"): one fp32 multiply per column"""
+    """dasac_upsample_softmax's `narrow` loop (upsample.hip, "tap_ac's column arithmetic, on the host"): one fp32 multiply per column"""
     sw = _ac_scale(w, W)
 
     def col(d):
@@ -69,7 +69,7 @@ def _narrow(w, W):
 
 
 def _grid(B, H, W, softmax):
-    """(grid.x, items per thread, waves that add a class-sum partial) of dasac_upsample_softmax (head.hip: `items`, `total` =
+    """(grid.x, items per thread, waves that add a class-sum partial) of dasac_upsample_softmax (upsample.hip: `items`, `total` =
     stream_grid(B * items, kHB, softmax ? kNumCu * 4 : kNumCu * 16) and `grid`); stream_grid is common.hpp's: ceil(work / block)
     clamped to [1, max_blocks]."""
     items = H * ((W + 3) // 4)

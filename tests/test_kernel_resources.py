@@ -108,15 +108,17 @@ def test_hot_gemm_loops_have_no_scratch_fit_their_occupancy_and_keep_their_instr
 
 # The streaming head kernels are issue-bound (tools/isa_count.py, profiles/EXPERIMENTS.md round 5): their occupancy arguments and
 # instruction diets are part of the design.  name fragment -> (VGPR budget, scratch bytes budget, VALU instructions in the kernel)
-HEAD = {
+UPSAMPLE = {
     "upsample_softmaxILi19ELb1ELb1EEE": (128, 32, 3400),      # probs path, up-factor 8: four waves per SIMD (was 225 VGPRs, ~4600 VALU)
     "upsample_softmaxILi19ELb0ELb1EEE": (64, 0, 1300),        # logits only: eight waves per SIMD (was 102 VGPRs, ~2500 VALU)
+}
+CROSS_ENTROPY = {
     "ce_bwd_rows_waveILi19ELi16EEE": (256, 0, 2800),          # two waves per SIMD, nothing spilled inside the row loop
 }
 POOL = {"maxpool_bwd_3s2p1": (64, 0, 200)}                    # 2 x 4 pixels per thread: ~170 VALU per 8 pixels (306 per 4 before)
 
 
-@pytest.mark.parametrize("src,table", [("head", HEAD), ("pool", POOL)])
+@pytest.mark.parametrize("src,table", [("upsample", UPSAMPLE), ("pool", POOL), ("cross_entropy", CROSS_ENTROPY)])
 def test_streaming_head_kernels_keep_their_registers_and_instruction_counts(tmp_path, src, table):
     txt = _asm(tmp_path, src)
     meta = _kernel_meta(txt)
