@@ -5,13 +5,10 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "chip.hpp"
 #include "dasac_hip.h"
 
 namespace dasac {
-
-constexpr int kWave = 64;          // CDNA4 wavefront
-constexpr int kNumXcd = 8;         // MI355X: 8 XCDs x 32 CUs
-constexpr int kNumCu = 256;
 
 int fail(int code, const char* fmt, ...);   // records dasac_last_error(), returns code
 

@@ -1,14 +1,15 @@
 // What the convolution files share (conv_gemm.hip, conv_wgrad.hip, conv_pack.hip, winograd.hip): vector types, tile constants,
 // the geometry both GEMM kernels take, buffer-descriptor loads, the split-bf16 operand helpers and the host's geometry checks.
+// The integer rules -- padding, tiles, schedules, splits, the block maps -- are conv_plan.hpp's.
 #pragma once
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace dasac {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBK = 16;            // K-step of the forward/dgrad kernel
 constexpr int kThreads = 256;      // 4 waves
 constexpr int kInvalid = 1 << 20;  // dh of a padded table row: never in bounds
 
@@ -35,7 +36,6 @@ struct GemmGeom {
 // used 2^31 as the poison).  The poison is the largest offset: always >= num_records, whatever scalar offset is added (the
 // hardware compares the per-lane offset with num_records - soffset), and never combined with an instruction immediate.
 constexpr unsigned kPoison = 0xFFFFFFFFu;
-constexpr int64_t kMaxTensorBytes = (1ll << 32) - 4096;
 constexpr int kRsrcFlags = 0x00020000;   // raw buffer, 32-bit data format (gfx9 family word 3)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -102,11 +102,5 @@ inline int fill_geom(GemmGeom& g, int Nb, int Cx, int H, int W, int OH, int OW, 
   g.w_bytes = 0;
   return DASAC_OK;
 }
-
-// M tile chosen from the padded channel count: 128 | 64 | 32
-inline int pick_bm(int Mpad) { return Mpad % 128 == 0 ? 128 : (Mpad % 64 == 0 ? 64 : 32); }
-
-// grids whose kernels read blockIdx.x % kNumXcd as the XCD are whole multiples of it
-inline int round_up_xcd(int n) { return (n + kNumXcd - 1) / kNumXcd * kNumXcd; }
 
 }  // namespace dasac

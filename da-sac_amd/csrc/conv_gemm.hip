@@ -5,7 +5,9 @@
 // 122,147-148,262-263; models/fcn.py:49,53,57,78,88) -- 1x1, dilated 3x3, 7x7/2 stem, and the
 // four-branch ASPP sum as ONE contraction -- for forward, data-gradient and weight-gradient.
 // This file: the forward / data-gradient GEMM with its three schedules.  conv_wgrad.hip: the weight gradient; conv_pack.hip: the gather
-// table and the weight packers; conv_expanded.hip: the tap-expanded ASPP path; conv_common.hpp: what they share.
+// table and the weight packers; conv_expanded.hip: the tap-expanded ASPP path; conv_common.hpp: what they share.  Which schedule a
+// launch gets, its grid and its workspace (gemm_plan) and the block maps of the three schedules are conv_plan.hpp's: plain C++,
+// compared with tests/gemm_schedule_ref.py and walked block by block on the host by tools/conv_plan_check.cpp.
 //
 //   forward / dgrad :  Out[m][pix] = sum_k  Wp[k][m] * gather(X, k, pix)        (conv_gemm)
 //   wgrad           :  G[m][k]     = sum_pix dZ[m][pix] * gather(X, k, pix)     (conv_wgrad)
@@ -25,14 +27,6 @@
 #include <type_traits>
 
 namespace dasac {
-
-constexpr int kSkWorkersPerCu = 3;                       // persistent 128x128 workers per CU (<=168 registers, 32 KB LDS each; four spill: EXPERIMENTS.md)
-constexpr int kSkWorkers = kNumCu * kSkWorkersPerCu;     // 768, multiple of 8: the grid of every stream-K launch
-constexpr int kTileSlots = kNumCu * 4;                   // resident blocks of the tile-per-block kernel (4 per CU)
-constexpr int kTailSlots = 2048;                         // deposit / flag slots of the split-K tail (SK == 2): 128 MB of workspace
-// workspace of the two hand-off schedules (128 x 128 tiles only): a deposit per slot of the larger one, then the flags
-constexpr size_t kPartialBytes = (size_t)(kTailSlots > kSkWorkers ? kTailSlots : kSkWorkers) * 128 * 128 * sizeof(float);
-inline size_t gemm_workspace_bytes() { return kPartialBytes + (size_t)(kTailSlots + 1) * sizeof(int); }
 
 #ifdef DASAC_TRACE_TILES
 // Diagnostic build only (tools/tile_timeline.py): per tile-per-block workgroup four s_memtime stamps -- start, first tile in LDS,
@@ -222,6 +216,12 @@ __global__ __launch_bounds__(kThreads, SK == 1 ? kSkWorkersPerCu : 4) void conv_
                                                  HANDOFF ? (STREAMK ? kSkWorkers : kTailSlots) * ACC_REGS * kThreads * 4 : 0);
 
   // ---- which part of the iteration space is mine --------------------------------------------
+  // one block per tile (SK == 0): conv_plan.hpp's map.  The two hand-off schedules keep their maps written out below: on the header's
+  // functions a timing row of each missed (profiles/conv_plan.md); tests/gemm_schedule_ref.py restates them.
+  // (written as one initialiser and one return at this level, not inside `if constexpr (SK == 0)`: only so do all instantiations
+  // keep the instruction streams they had with the map written inline, profiles/conv_plan.md section 3)
+  const GemmWork tile_work = SK == 0 ? gemm_tile_work(blockIdx.x, m_tiles, n_tiles, KT) : GemmWork{true, 0, 0};
+  if (!tile_work.has_work) return;
   // block b runs on XCD b%8: tiles (or ranges) that are adjacent -- same activation tile, next M tile --
   // go to the same XCD so that they share its L2.
   const int bid = blockIdx.x;
@@ -233,7 +233,10 @@ __global__ __launch_bounds__(kThreads, SK == 1 ? kSkWorkersPerCu : 4) void conv_
   // (the first sk_rem ranges get the extra one): range r starts at r * sk_per + min(r, sk_rem)
   int sk_per = 0, sk_rem = 0;
   auto sk_start = [&](int r) { return r * sk_per + min(r, sk_rem); };
-  if (STREAMK) {
+  if (SK == 0) {
+    it = tile_work.it;
+    it_end = tile_work.it_end;
+  } else if (STREAMK) {
     const int G = gridDim.x;
     my_range = xcd * (G / kNumXcd) + slot;
     const int sk_total = m_tiles * n_tiles * KT;             // < 2^31 (checked by the host)
@@ -245,7 +248,7 @@ __global__ __launch_bounds__(kThreads, SK == 1 ? kSkWorkersPerCu : 4) void conv_
     // each XCD owns a CONTIGUOUS run of pixel tiles (spatial neighbours share halo rows in its L2)
     const int per_xcd = (n_tiles + kNumXcd - 1) / kNumXcd;
     const int lead_blocks = per_xcd * kNumXcd * m_tiles;       // == gridDim.x without a tail
-    if (!TAIL || bid < lead_blocks) {
+    if (bid < lead_blocks) {
       const int n_local = slot / m_tiles;
       const int n_tile = xcd * per_xcd + n_local;
       if (n_local >= per_xcd || n_tile >= n_tiles) return;
@@ -718,10 +721,9 @@ __global__ __launch_bounds__(kThreads, SK == 1 ? kSkWorkersPerCu : 4) void conv_
   } while (STREAMK && it < it_end);
 }
 
-// stream-K pays when the tile count leaves the last round of resident blocks mostly empty.
 // The persistent grid (3 workers per CU x 256 CUs) and the XCD mapping are sized for the full MI355X; a device with
 // fewer CUs (partitioned modes, other parts) gets the tile-per-block schedule only.  The answer is per device id
-// (a process may drive several devices / switch with hipSetDevice).
+// (a process may drive several devices / switch with hipSetDevice).  It is gemm_plan's `full_chip` (conv_plan.hpp).
 static bool persistent_grid_fits() {
   constexpr int kMaxDev = 64;
   static std::atomic<signed char> cache[kMaxDev];          // 0 unknown, 1 fits, -1 does not
@@ -736,87 +738,29 @@ static bool persistent_grid_fits() {
   return ok;
 }
 
-// workers of a persistent stream-K launch: 3 per CU on the CUs this process does not leave to overlapped collectives.  `reserved` is
-// read ONCE per launch decision (reserved_cus()) and handed through: a concurrent dasac_set_reserved_cus must not make the
-// eligibility test, the schedule choice and the grid size of one launch disagree.
-static int sk_workers(int reserved) { return (kNumCu - reserved) * kSkWorkersPerCu; }
-
-static bool want_streamk(int tiles, int k_steps, int reserved) {
-  if (!persistent_grid_fits()) return false;
-  if ((long long)tiles * k_steps < sk_workers(reserved)) return false;                  // every range gets >= 1 K-step
-  // measured: the persistent schedule (3 workers/CU, <=168 registers) wins on long contractions whose tile count
-  // fills the last round of the plain launch badly; short-K 1x1 layers are better off with the plain kernel's
-  // 4 blocks per CU (128 registers) even with a partly empty last round (85 vs 99 TFLOP/s at K = 256) -- unless
-  // the launch would leave most of the chip idle (small batches: 296 tiles at B = 2, 148 at B = 1).
-  const int resident = (kNumCu - reserved) * 3;
-  const int rounds = (tiles + resident - 1) / resident;
-  const double eff = (double)tiles / ((double)rounds * resident);
-  return k_steps >= 64 ? eff < 0.93 : (k_steps >= 16 && eff < 0.6);
-}
-
-// Split-K tail (SK == 2) of a launch over ALL n_tiles pixel tiles: the leading whole rounds of resident blocks run one block per
-// tile, the remaining R tiles are cut into `split` K-ranges so that the pieces fill (a whole number of) rounds again.  Chosen for
-// the shapes the persistent schedule was chosen for in rounds 2-5 (want_streamk) when at least one whole round leads.  The split
-// minimises rounds x (K-steps per piece + a piece's fixed cost: prologue, deposit or epilogue ~ 6 K-steps).  Returns 0 = no tail.
-static int tail_plan(int m_tiles, int n_tiles, int k_steps, int reserved, int& lead_n) {
-  const int tiles = m_tiles * n_tiles;
-  if (!want_streamk(tiles, k_steps, reserved)) return 0;
-  lead_n = (tiles / kTileSlots) * kTileSlots / m_tiles;          // pixel tiles of the leading whole rounds
-  // (fewer tiles than resident blocks -- small batches, cfg-2's 296 tiles -- stay on the persistent kernel: the same launches as pure
-  // split-K pieces of this kernel, 4 blocks per CU, measured 35.4 against 33.9 ms per cfg-2 step: equal ranges balance better than
-  // equal pieces when nothing leads; profiles/EXPERIMENTS.md round 6)
-  if (lead_n <= 0 || lead_n >= n_tiles) return 0;
-  const int R = (n_tiles - lead_n) * m_tiles;
-  int best = 0;
-  double best_cost = 0.0;
-  // (a sweep of the minimum piece length 8 .. 32 K-steps and of the fixed cost 6 .. 20 moved the three tail shapes of the step by
-  // less than 1 %: tools/experiments/r6_tail_sweep.sh, EXPERIMENTS.md)
-  constexpr int min_steps = 8;
-  constexpr double ovh = 6.0;
-  for (int sp = 1; sp <= 8 && sp * min_steps <= k_steps; ++sp) {
-    if ((long long)R * (sp - 1) > kTailSlots) break;
-    const int rounds = (R * sp + kTileSlots - 1) / kTileSlots;
-    const double cost = rounds * ((double)k_steps / sp + ovh);
-    if (best == 0 || cost < best_cost - 1e-9) {
-      best = sp;
-      best_cost = cost;
-    }
-  }
-  return best;
-}
-
-// `n_tiles` pixel tiles starting at g.n_tile0; schedule 0 = pick (split-K tail over a whole tensor, else want_streamk), 1 = one
-// block per tile, 2 = stream-K
+// one launch by its plan (conv_plan.hpp: gemm_plan); g.n_tile0 is the plan's
 template <int BM, int BN, int WAVES_M, int BK, bool FAST, bool X3 = false, int BITS = 0>
-static int launch_gemm(const float* X, const float* Wp, const int4* tab, float* Out, const GemmGeom& g,
-                       const Epilogue& ep, int n_tiles, int schedule, void* workspace, size_t ws_bytes, hipStream_t s) {
-  const int m_tiles = (g.M + BM - 1) / BM;
-  if ((long long)m_tiles * (n_tiles + kNumXcd) * (g.Kpad / BK) >= (1ll << 31)) return fail(DASAC_EINVAL, "conv_gemm: iteration space exceeds 2^31");
-  const int reserved = reserved_cus();
-  const size_t need = gemm_workspace_bytes();
-  float* partial = reinterpret_cast<float*>(workspace);
-  int* flags = reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + kPartialBytes);
-  if constexpr (BM == 128) {
-    const bool whole = g.n_tile0 == 0 && (long long)n_tiles * BN >= g.Npix;
-    int lead_n = 0;
-    const int split = (schedule == 0 && whole && workspace && persistent_grid_fits()) ? tail_plan(m_tiles, n_tiles, g.Kpad / BK, reserved, lead_n) : 0;
-    if (split > 0) {
-      if (ws_bytes < need) return fail(DASAC_EWORKSPACE, "conv_gemm: workspace too small (%zu < %zu)", ws_bytes, need);
-      const int R = (n_tiles - lead_n) * m_tiles;
-      hipLaunchKernelGGL((conv_gemm<BM, BN, WAVES_M, BK, FAST, 2, X3, BITS>), dim3(round_up_xcd(lead_n) * m_tiles + round_up_xcd(R) * split),
-                         dim3(kThreads), 0, s, X, Wp, tab, Out, g, ep, m_tiles, lead_n, partial, flags, R, split);
-      return DASAC_OK;
-    }
+static int launch_gemm(const float* X, const float* Wp, const int4* tab, float* Out, const GemmGeom& g, const Epilogue& ep,
+                       const GemmPlan& p, void* workspace, size_t ws_bytes, hipStream_t s) {
+  if ((long long)p.m_tiles * (p.n_tiles + kNumXcd) * p.k_steps >= (1ll << 31)) return fail(DASAC_EINVAL, "conv_gemm: iteration space exceeds 2^31");
+  if (ws_bytes < p.workspace_bytes) return fail(DASAC_EWORKSPACE, "conv_gemm: workspace too small (%zu < %zu)", ws_bytes, p.workspace_bytes);
+  float* partial = p.uses_workspace ? reinterpret_cast<float*>(workspace) : nullptr;
+  int* flags = p.uses_workspace ? reinterpret_cast<int*>(reinterpret_cast<char*>(workspace) + kPartialBytes) : nullptr;
+  switch (p.kind) {
+    case kGemmTail:
+      if constexpr (BM == 128)
+        hipLaunchKernelGGL((conv_gemm<BM, BN, WAVES_M, BK, FAST, 2, X3, BITS>), dim3(p.grid), dim3(kThreads), 0, s, X, Wp, tab, Out, g, ep,
+                           p.m_tiles, p.lead_n, partial, flags, p.tail_tiles, p.split);
+      break;
+    case kGemmStreamK:
+      if constexpr (BM == 128)
+        hipLaunchKernelGGL((conv_gemm<BM, BN, WAVES_M, BK, FAST, 1, X3, BITS>), dim3(p.grid), dim3(kThreads), 0, s, X, Wp, tab, Out, g, ep,
+                           p.m_tiles, p.n_tiles, partial, flags, 0, 1);
+      break;
+    default:
+      hipLaunchKernelGGL((conv_gemm<BM, BN, WAVES_M, BK, FAST, 0, X3, BITS>), dim3(p.grid), dim3(kThreads), 0, s, X, Wp, tab, Out, g, ep,
+                         p.m_tiles, p.n_tiles, nullptr, nullptr, 0, 1);
   }
-  const bool sk_ok = BM == 128 && workspace && (long long)m_tiles * n_tiles * (g.Kpad / BK) >= sk_workers(reserved) && persistent_grid_fits();
-  if (sk_ok && (schedule == 2 || (schedule == 0 && want_streamk(m_tiles * n_tiles, g.Kpad / BK, reserved)))) {
-    if (ws_bytes < need) return fail(DASAC_EWORKSPACE, "conv_gemm: workspace too small (%zu < %zu)", ws_bytes, need);
-    hipLaunchKernelGGL((conv_gemm<BM, BN, WAVES_M, BK, FAST, 1, X3, BITS>), dim3(sk_workers(reserved)), dim3(kThreads), 0, s, X, Wp, tab, Out, g,
-                       ep, m_tiles, n_tiles, partial, flags, 0, 1);
-    return DASAC_OK;
-  }
-  hipLaunchKernelGGL((conv_gemm<BM, BN, WAVES_M, BK, FAST, 0, X3, BITS>), dim3(round_up_xcd(n_tiles) * m_tiles), dim3(kThreads), 0, s, X, Wp,
-                     tab, Out, g, ep, m_tiles, n_tiles, nullptr, nullptr, 0, 1);
   return DASAC_OK;
 }
 
@@ -824,31 +768,26 @@ static int launch_gemm(const float* X, const float* Wp, const int4* tab, float* 
 
 using namespace dasac;
 
-// 1 when dasac_conv_gemm (given a workspace) runs this shape on the persistent stream-K schedule
-extern "C" int dasac_conv_gemm_schedule(int Nb, int OH, int OW, int M, int K) {
-  const int Mpad = dasac_conv_mpad(M);
-  if (pick_bm(Mpad) != 128) return 0;
-  const int tiles = ((M + 127) / 128) * ((Nb * OH * OW + 127) / 128);
-  return want_streamk(tiles, (K + kBK - 1) / kBK, reserved_cus()) ? 1 : 0;
+// the plan of dasac_conv_gemm over the whole tensor with a workspace, schedule 0: what the three queries below report
+static GemmPlan whole_plan(int Nb, int OH, int OW, int M, int K) {
+  const int64_t Npix = (int64_t)Nb * OH * OW;
+  return gemm_plan(M, K, Npix, 0, Npix, 0, true, reserved_cus(), persistent_grid_fits());
 }
+
+// 1 when this shape's own schedule is the persistent stream-K one (a split-K tail, where dasac_conv_gemm_tail_split finds one,
+// goes first)
+extern "C" int dasac_conv_gemm_schedule(int Nb, int OH, int OW, int M, int K) { return whole_plan(Nb, OH, OW, M, K).wants_streamk ? 1 : 0; }
 
 // (Rounds 2-5 issued a long-K conv whose tile count leaves a ragged last round as TWO launches -- whole rounds one block per tile,
 // the remainder on the persistent stream-K schedule (dasac_conv_gemm_plan) -- so that the lockstep K walk of the leading rounds
-// keeps sharing halo rows in L2.  Round 6 folded the remainder into the first launch: tail_plan / conv_gemm<SK = 2> above.
+// keeps sharing halo rows in L2.  Round 6 folded the remainder into the first launch: tail_plan / conv_gemm<SK = 2>.
 // Measured on one box, cfg-3 fused step: GEMM kernel time 273.5 -> 272.6 ms, 169 launches per step gone; a piece's prologue and
 // deposit / epilogue cost what the second launch's ramp and hand-off did: profiles/r6_tail_and_qtap_ab.txt.)
-extern "C" size_t dasac_conv_gemm_workspace(void) {
-  return gemm_workspace_bytes();
-}
+extern "C" size_t dasac_conv_gemm_workspace(void) { return kGemmWorkspaceBytes; }
 
 // K-ranges per tail tile when dasac_conv_gemm (schedule 0, whole tensor, workspace given) runs this shape as ONE launch of whole
 // rounds of tile-per-block workgroups + a split-K tail; 0 = it does not (then dasac_conv_gemm_schedule tells the rest)
-extern "C" int dasac_conv_gemm_tail_split(int Nb, int OH, int OW, int M, int K) {
-  const int Mpad = dasac_conv_mpad(M);
-  if (pick_bm(Mpad) != 128 || !persistent_grid_fits()) return 0;
-  int lead_n = 0;
-  return tail_plan((M + 127) / 128, (int)(((int64_t)Nb * OH * OW + 127) / 128), (K + kBK - 1) / kBK, reserved_cus(), lead_n);
-}
+extern "C" int dasac_conv_gemm_tail_split(int Nb, int OH, int OW, int M, int K) { return whole_plan(Nb, OH, OW, M, K).split; }
 
 #ifdef DASAC_TRACE_TILES
 extern "C" int dasac_debug_set_tile_trace(void* buffer) {
@@ -887,43 +826,43 @@ static int conv_gemm_impl(bool x3, const float* x, const float* packed, const in
   const int4* tab = reinterpret_cast<const int4*>(table);
   hipStream_t s = as_stream(stream);
   const bool fast = Cx % kBK == 0;      // a K-step never straddles two taps
-  const int bm = pick_bm(Mpad);
   // pixel range of this launch (whole tiles; the last one may be ragged only at the end of the tensor)
-  const int bn = bm == 32 ? 256 : 128;
   const int pix_end = pix_count > 0 ? pix_begin + pix_count : g.Npix;
   DASAC_REQUIRE(schedule >= 0 && schedule <= 2, "conv_gemm: schedule must be 0 (auto), 1 (tile per block) or 2 (stream-K)");
+  const int bm = pick_bm(Mpad), bn = bm == 32 ? 256 : 128;
   DASAC_REQUIRE(pix_begin >= 0 && pix_begin < g.Npix && pix_begin % bn == 0 && pix_end > pix_begin && pix_end <= g.Npix &&
                     (pix_end == g.Npix || pix_end % bn == 0),
                 "conv_gemm: pixel range [%d, %d) must consist of whole %d-pixel tiles", pix_begin, pix_end, bn);
-  g.n_tile0 = pix_begin / bn;
-  const int n_tiles = (pix_end - pix_begin + bn - 1) / bn;
+  // the 64- and 32-row tiles have the tile-per-block kernel only: their plan is that whatever was asked for
+  const GemmPlan p = gemm_plan(M, K, g.Npix, pix_begin, pix_end, schedule, workspace != nullptr, reserved_cus(), persistent_grid_fits());
+  g.n_tile0 = p.n_tile0;
   const char* what = "conv_gemm";
   if (x3) {
     DASAC_REQUIRE(bm >= 64, "conv_gemm_x3: needs M > 32 (use dasac_conv_gemm for skinny outputs)");
     what = "conv_gemm_x3";
     if (bm == 128)
-      rc = fast ? launch_gemm<128, 128, 2, kBK, true, true>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s)
-                : launch_gemm<128, 128, 2, kBK, false, true>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s);
+      rc = fast ? launch_gemm<128, 128, 2, kBK, true, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s)
+                : launch_gemm<128, 128, 2, kBK, false, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
     else
-      rc = fast ? launch_gemm<64, 128, 2, kBK, true, true>(x, packed, tab, out, g, ep, n_tiles, 1, nullptr, 0, s)
-                : launch_gemm<64, 128, 2, kBK, false, true>(x, packed, tab, out, g, ep, n_tiles, 1, nullptr, 0, s);
+      rc = fast ? launch_gemm<64, 128, 2, kBK, true, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s)
+                : launch_gemm<64, 128, 2, kBK, false, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
   } else if (stats) {
     what = "conv_gemm_stats";
-    rc = launch_gemm<128, 128, 2, kBK, true, false, 3>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s);
+    rc = launch_gemm<128, 128, 2, kBK, true, false, 3>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
   } else if (mask_bits || relu_bits_out) {
     DASAC_REQUIRE(dasac_conv_gemm_bits_ok(M, Cx) && !(mask_bits && relu_bits_out),
                   "conv_gemm: bit masks need the 128-row fp32 tile with Cx %% 16 == 0 (dasac_conv_gemm_bits_ok), one direction per call");
-    rc = relu_bits_out ? launch_gemm<128, 128, 2, kBK, true, false, 1>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s)
-                       : launch_gemm<128, 128, 2, kBK, true, false, 2>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s);
+    rc = relu_bits_out ? launch_gemm<128, 128, 2, kBK, true, false, 1>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s)
+                       : launch_gemm<128, 128, 2, kBK, true, false, 2>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
   } else if (bm == 128) {
-    rc = fast ? launch_gemm<128, 128, 2, kBK, true>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s)
-              : launch_gemm<128, 128, 2, kBK, false>(x, packed, tab, out, g, ep, n_tiles, schedule, workspace, ws_bytes, s);
+    rc = fast ? launch_gemm<128, 128, 2, kBK, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s)
+              : launch_gemm<128, 128, 2, kBK, false>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
   } else if (bm == 64) {
-    rc = fast ? launch_gemm<64, 128, 2, kBK, true>(x, packed, tab, out, g, ep, n_tiles, 1, nullptr, 0, s)
-              : launch_gemm<64, 128, 2, kBK, false>(x, packed, tab, out, g, ep, n_tiles, 1, nullptr, 0, s);
+    rc = fast ? launch_gemm<64, 128, 2, kBK, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s)
+              : launch_gemm<64, 128, 2, kBK, false>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
   } else {
-    rc = fast ? launch_gemm<32, 256, 1, kBK, true>(x, packed, tab, out, g, ep, n_tiles, 1, nullptr, 0, s)
-              : launch_gemm<32, 256, 1, kBK, false>(x, packed, tab, out, g, ep, n_tiles, 1, nullptr, 0, s);
+    rc = fast ? launch_gemm<32, 256, 1, kBK, true>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s)
+              : launch_gemm<32, 256, 1, kBK, false>(x, packed, tab, out, g, ep, p, workspace, ws_bytes, s);
   }
   if (rc) return rc;
   DASAC_CHECK_LAUNCH(what);

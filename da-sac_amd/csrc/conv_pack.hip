@@ -132,8 +132,8 @@ __global__ void pack_x3(const f32x4u* Wp, f32x4u* Wx, int Mpad, int Kpad) {   //
 
 using namespace dasac;
 
-extern "C" int dasac_conv_mpad(int M) { return M > 64 ? (M + 127) / 128 * 128 : (M > 32 ? 64 : 32); }
-extern "C" int dasac_conv_kpad(int K) { return (K + 127) / 128 * 128; }
+extern "C" int dasac_conv_mpad(int M) { return conv_mpad(M); }
+extern "C" int dasac_conv_kpad(int K) { return conv_kpad(K); }
 
 extern "C" int dasac_conv_table(const int32_t* kh, const int32_t* kw, const int32_t* dil, const int32_t* pad,
                                 int n_branches, int C, int plane_h, int plane_w, int transposed, int order, int32_t* table,

@@ -3,6 +3,8 @@
 // as per-split partial slabs (conv_wgrad; conv_wgrad_batched for the 16 point contractions of a Winograd weight gradient) and the
 // fixed-order reductions of those slabs into dW.  Replaces the weight half of autograd's convolution backward for every nn.Conv2d of
 // the reference backbone (models/deeplabv2.py:59,65-66,70,107; models/fcn.py:49,53,57,78,88).
+// Tiles, pixel splits, grid and workspace layout of a launch (wgrad_plan, wgrad_batched_plan) and the block map both kernels decode
+// their block id with are conv_plan.hpp's: plain C++, walked on the host by tools/conv_plan_check.cpp.
 #include "conv_common.hpp"
 
 namespace dasac {
@@ -13,7 +15,6 @@ namespace dasac {
 // LDS tiles keep the natural [row][pix] order with an odd row pitch (33) so that both the
 // coalesced tile writes and the strided MFMA operand reads are bank-conflict free.
 // ------------------------------------------------------------------------------------------
-constexpr int kWgPix = 32;   // pixels per K-step
 constexpr int kWgPitch = 36;   // row pitch (floats): 16-byte aligned rows, 16 consecutive rows x 4 dwords hit 64 distinct banks
 
 // FAST: Cx % BN == 0 (the 128 im2col rows of a block belong to ONE tap) and M % 8 == 0: one (dh, dw)
@@ -40,14 +41,12 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad(const float* __restric
   __shared__ __attribute__((aligned(16))) float sA[1][X3 ? 32 * PA : BM * kWgPitch];   // X3: [head|tail][4 octets][PA] x 16 B
   __shared__ __attribute__((aligned(16))) float sB[1][X3 ? 32 * PB : BN * kWgPitch];
 
-  // block b runs on XCD b % 8: give every XCD a CONTIGUOUS run of the (split-major) block list, so that the tiles of a
-  // pixel split -- which all stream the same dZ and X pixels -- meet in one L2 instead of being fetched by all eight
+  // which (m tile, k tile, pixel split) is mine: conv_plan.hpp
   const int n_blocks = m_tiles * k_tiles * n_splits;
-  const int per_xcd = (n_blocks + kNumXcd - 1) / kNumXcd;
-  const int lb = ((int)blockIdx.x % kNumXcd) * per_xcd + (int)blockIdx.x / kNumXcd;
+  const int lb = wgrad_list_index(blockIdx.x, n_blocks);
   if (lb >= n_blocks) return;
-  const int tile = lb % (m_tiles * k_tiles), split = lb / (m_tiles * k_tiles);
-  const int m_tile = tile % m_tiles, k_tile = tile / m_tiles;
+  const WgradTile work = wgrad_tile(lb, m_tiles, k_tiles);
+  const int m_tile = work.m_tile, k_tile = work.k_tile, split = work.split;
   const int m0 = m_tile * BM, kb0 = k_tile * BN;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);   // wave-uniform on purpose: scalar buffer offsets
@@ -60,8 +59,8 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad(const float* __restric
 
   const int OHW = g.OH * g.OW;
   const int planeHW = g.H * g.W;
-  const int p_begin = split * pix_per_split;
-  const int p_end = min(p_begin + pix_per_split, g.Npix);
+  const PixelRange px = wgrad_pixels(split, pix_per_split, g.Npix);
+  const int p_begin = px.begin, p_end = px.end;
   const int steps = (p_end - p_begin + kWgPix - 1) / kWgPix;
 
   // generic path: table rows of this thread's B loads are fixed for the whole kernel (offset, dh:dw packed)
@@ -407,12 +406,11 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad_batched(const float* _
   __shared__ __attribute__((aligned(16))) float sB[BN * kWgPitch];
 
   const int n_blocks = w.m_tiles * w.k_tiles * w.n_splits;
-  const int per_xcd = (n_blocks + kNumXcd - 1) / kNumXcd;
-  const int lb = ((int)blockIdx.x % kNumXcd) * per_xcd + (int)blockIdx.x / kNumXcd;
+  const int lb = wgrad_list_index(blockIdx.x, n_blocks);
   if (lb >= n_blocks) return;
+  const WgradTile work = wgrad_tile(lb, w.m_tiles, w.k_tiles);
   const int entry = blockIdx.y;
-  const int tile = lb % (w.m_tiles * w.k_tiles), split = lb / (w.m_tiles * w.k_tiles);
-  const int m_tile = tile % w.m_tiles, k_tile = tile / w.m_tiles;
+  const int m_tile = work.m_tile, k_tile = work.k_tile, split = work.split;
   const int m0 = m_tile * BM, kb0 = k_tile * BN;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -424,8 +422,8 @@ __global__ __launch_bounds__(kThreads, 3) void conv_wgrad_batched(const float* _
   const __amdgpu_buffer_rsrc_t ra = make_rsrc(A + (size_t)entry * w.a_stride, (unsigned)(w.M * w.T) * 4u);
   const __amdgpu_buffer_rsrc_t rb = make_rsrc(B + (size_t)entry * w.b_stride, (unsigned)(w.C * w.T) * 4u);
 
-  const int p_begin = split * w.pix_per_split;
-  const int p_end = min(p_begin + w.pix_per_split, w.T);
+  const PixelRange px = wgrad_pixels(split, w.pix_per_split, w.T);
+  const int p_begin = px.begin, p_end = px.end;
   const int steps = (p_end - p_begin + kWgPix - 1) / kWgPix;
   const bool do_sums = (k_tile == 0) && (entry == w.sum_entry);
 
@@ -730,83 +728,21 @@ __global__ __launch_bounds__(256) void wgrad_reduce_expanded(const float* __rest
 
 template <int BM, int BN, int WAVES_M, bool FAST>
 static void launch_wgrad(bool x3, const float* dZ, const float* X, const int4* tab, float* P, float* Psum, const GemmGeom& g,
-                         int splits, int pix_per_split, hipStream_t s) {
-  const int m_tiles = g.Mpad / BM, k_tiles = g.Kpad / BN;
-  const int grid = round_up_xcd(m_tiles * k_tiles * splits);
+                         const WgradPlan& p, hipStream_t s) {
   if (x3)
-    hipLaunchKernelGGL((conv_wgrad<BM, BN, WAVES_M, FAST, true>), dim3(grid), dim3(kThreads), 0, s, dZ, X, tab, P,
-                       Psum, g, m_tiles, k_tiles, splits, pix_per_split);
+    hipLaunchKernelGGL((conv_wgrad<BM, BN, WAVES_M, FAST, true>), dim3(p.grid), dim3(kThreads), 0, s, dZ, X, tab, P,
+                       Psum, g, p.m_tiles, p.k_tiles, p.splits, p.per);
   else
-    hipLaunchKernelGGL((conv_wgrad<BM, BN, WAVES_M, FAST, false>), dim3(grid), dim3(kThreads), 0, s, dZ, X, tab, P,
-                       Psum, g, m_tiles, k_tiles, splits, pix_per_split);
+    hipLaunchKernelGGL((conv_wgrad<BM, BN, WAVES_M, FAST, false>), dim3(p.grid), dim3(kThreads), 0, s, dZ, X, tab, P,
+                       Psum, g, p.m_tiles, p.k_tiles, p.splits, p.per);
 }
 
 }  // namespace dasac
 
 using namespace dasac;
 
-// Number of pixel splits: every block of a wgrad launch runs for the same time, so pick the split count
-// whose block total fills whole rounds of resident blocks (2 per CU for the 128-row tile, 3 otherwise).
-static int wgrad_bn(int Cx) { return (Cx % 128 != 0 && Cx % 64 == 0) ? 64 : 128; }   // k-tile rows: one tap per tile when possible
-
-// 3 resident blocks per CU (<= 168 registers).  Measured in round 3: both 128x128 kernels also fit 128 registers (2 / 44 spill
-// instructions outside the MFMA loop) and 4 x 36 KB of LDS, but at 4 blocks per CU the step's weight-gradient time goes from
-// 109.2 to 114.0 ms (123.1 -> 117.9 TFLOP/s): occupancy is not what the pixel loop lacks.  Nor is it the dZ loads of the 3x3
-// layers: dZ through the four-pixels-per-lane loader (dwordx4 + ds_write_b128, the gathered operand unchanged) gives 109.6 vs
-// 109.1 ms.
-static int fill_rounds(int tiles, int max_splits, int slots) {   // the split count in 1..max_splits whose blocks fill whole rounds
-  int best = 1;
-  double best_eff = 0.0;
-  for (int sp = 1; sp <= max_splits; ++sp) {
-    const int blocks = tiles * sp;
-    const int rounds = (blocks + slots - 1) / slots;
-    const double eff = (double)blocks / ((double)rounds * slots);
-    if (eff > best_eff + 0.02) {                             // prefer fewer splits unless clearly better
-      best_eff = eff;
-      best = sp;
-    }
-  }
-  return best;
-}
-
-static int wgrad_splits(int Mpad, int Kpad, int Npix, int BM, int BNk = 128) {
-  const int tiles = (Mpad / BM) * (Kpad / BNk);
-  const int slots = kNumCu * 3;
-  // At least 256 pixels (8 K-steps) per split.  Rounds 1-3 asked for 1024: at batch 2 (cfg-2: 18 818 pixels) that capped the 16-tile
-  // 1x1 layers at 19 splits = 304 blocks for 768 slots; measured in round 4 (profiles/r4_wgrad_split_granularity.txt, cfg-2):
-  // 1024 -> 512 -> 256 pixels: weight gradients 18.7 -> 16.3 -> 15.4 ms/step (90 -> 103 -> 109 TFLOP/s).  Large batches are
-  // unaffected (the cap of 64 splits binds first).
-  constexpr int kMinPix = 256;
-  int max_splits = (Npix + kMinPix - 1) / kMinPix;
-  // few tiles x many pixels (layer1 / stem: 2 tiles, 298k..1.2M pixels): more splits, or 128 blocks would face 768 slots
-  const int cap = (tiles < 12 && Npix >= 200000) ? (slots + tiles - 1) / tiles : 64;   // measured: no gain at 97x97 resolution
-  if (max_splits > cap) max_splits = cap;
-  return fill_rounds(tiles, max_splits, slots);
-}
-
-// Where a weight-gradient launch puts its slabs: the M tile, the k-tile width (one tap per tile when the channel count allows) and the
-// pixel split count.  conv_wgrad writes by it and the finishers find Psum behind `splits` slabs by it: one rule, because two spellings
-// that drift apart would read the wrong slab silently.
-struct WgradLayout {
-  int Mpad, Kpad, bm, bnk, splits;
-};
-static WgradLayout wgrad_layout(int M, int K, int Cx, int Npix) {
-  WgradLayout l;
-  l.Mpad = dasac_conv_mpad(M);
-  l.Kpad = dasac_conv_kpad(K);
-  l.bm = pick_bm(l.Mpad);
-  l.bnk = (M % 8 == 0 && l.bm != 32) ? wgrad_bn(Cx) : 128;
-  l.splits = wgrad_splits(l.Mpad, l.Kpad, Npix, l.bm, l.bnk);
-  return l;
-}
-
-extern "C" size_t dasac_conv_wgrad_workspace(int Nb, int OH, int OW, int M, int K) {
-  const int Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K);
-  // upper bound over both k-tile widths (the width depends on Cx, unknown here)
-  const int s128 = wgrad_splits(Mpad, Kpad, Nb * OH * OW, pick_bm(Mpad), 128), s64 = wgrad_splits(Mpad, Kpad, Nb * OH * OW, pick_bm(Mpad), 64);
-  const int splits = s128 > s64 ? s128 : s64;
-  return (size_t)splits * Mpad * (Kpad + 1) * sizeof(float);     // slabs + per-split channel sums
-}
+// (the size does not depend on the gathered channel count: the bound over both k-tile widths)
+extern "C" size_t dasac_conv_wgrad_workspace(int Nb, int OH, int OW, int M, int K) { return wgrad_plan(M, K, 0, Nb * OH * OW).workspace_bytes; }
 
 // dz [Nb,M,OH,OW], x [Nb,Cx,H,W] -> slabs in workspace -> dW (one or several weight tensors of a fused conv)
 static int conv_wgrad_impl(bool x3, const float* dz, const float* x, const int32_t* table, int Nb, int Cx, int H, int W, int OH,
@@ -814,24 +750,21 @@ static int conv_wgrad_impl(bool x3, const float* dz, const float* x, const int32
   DASAC_REQUIRE(dz && x && table && workspace, "conv_wgrad: null pointer");
   DASAC_REQUIRE(((uintptr_t)table & 15) == 0, "conv_wgrad: misaligned table (16-byte rows)");
   GemmGeom g;
-  const int Mpad = dasac_conv_mpad(M), Kpad = dasac_conv_kpad(K);
-  int rc = fill_geom(g, Nb, Cx, H, W, OH, OW, stride, M, Mpad, Kpad, OH, OW, 1);
+  int rc = fill_geom(g, Nb, Cx, H, W, OH, OW, stride, M, conv_mpad(M), conv_kpad(K), OH, OW, 1);
   if (rc) return rc;
-  const WgradLayout l = wgrad_layout(M, K, Cx, g.Npix);
-  const int bm = l.bm, bnk = l.bnk, splits = l.splits;
+  const WgradPlan p = wgrad_plan(M, K, Cx, g.Npix);
+  const int bm = p.bm;
   // the size function itself (the larger of both k-tile widths' split counts, so never less than this launch writes): what it
   // states is what is asked for, whatever Cx turns out to be
-  if (ws_bytes < dasac_conv_wgrad_workspace(Nb, OH, OW, M, K)) return fail(DASAC_EWORKSPACE, "conv_wgrad: workspace too small");
-  int per = (g.Npix + splits - 1) / splits;
-  per = (per + kWgPix - 1) / kWgPix * kWgPix;
+  if (ws_bytes < p.workspace_bytes) return fail(DASAC_EWORKSPACE, "conv_wgrad: workspace too small");
   const int4* tab = reinterpret_cast<const int4*>(table);
   float* P = reinterpret_cast<float*>(workspace);
-  float* Psum = P + (size_t)splits * Mpad * Kpad;
+  float* Psum = P + p.psum_offset;
   hipStream_t s = as_stream(stream);
   const bool fast = (Cx % 128 == 0) && (M % 8 == 0);   // a 128-row k tile sits inside one tap
-  if (bnk == 64) {                                     // Cx = 64, 192, ...: 64-row k tiles, still one tap each
-    if (bm == 128) launch_wgrad<128, 64, 2, true>(x3, dz, x, tab, P, Psum, g, splits, per, s);
-    else launch_wgrad<64, 64, 2, true>(x3, dz, x, tab, P, Psum, g, splits, per, s);
+  if (p.bnk == 64) {                                   // Cx = 64, 192, ...: 64-row k tiles, still one tap each
+    if (bm == 128) launch_wgrad<128, 64, 2, true>(x3, dz, x, tab, P, Psum, g, p, s);
+    else launch_wgrad<64, 64, 2, true>(x3, dz, x, tab, P, Psum, g, p, s);
     DASAC_CHECK_LAUNCH("conv_wgrad");
     return DASAC_OK;
   }
@@ -843,23 +776,21 @@ static int conv_wgrad_impl(bool x3, const float* dz, const float* x, const int32
       // "same"-padded k x k layers (every 3x3 of the bottlenecks): the quad loader with per-pixel tap validity (QTAP)
       const bool qtap = same && K > Cx && K % Cx == 0 && W >= 4;
       if (quad || qtap) {
-        const int m_tiles = g.Mpad / 128, k_tiles = g.Kpad / 128;
-        const int grid = round_up_xcd(m_tiles * k_tiles * splits);
         if (quad)
-          hipLaunchKernelGGL((conv_wgrad<128, 128, 2, true, false, true, false>), dim3(grid), dim3(kThreads), 0, s, dz, x, tab, P, Psum, g,
-                             m_tiles, k_tiles, splits, per);
+          hipLaunchKernelGGL((conv_wgrad<128, 128, 2, true, false, true, false>), dim3(p.grid), dim3(kThreads), 0, s, dz, x, tab, P, Psum, g,
+                             p.m_tiles, p.k_tiles, p.splits, p.per);
         else
-          hipLaunchKernelGGL((conv_wgrad<128, 128, 2, true, false, true, true>), dim3(grid), dim3(kThreads), 0, s, dz, x, tab, P, Psum, g,
-                             m_tiles, k_tiles, splits, per);
-      } else if (fast) launch_wgrad<128, 128, 2, true>(x3, dz, x, tab, P, Psum, g, splits, per, s);
-      else launch_wgrad<128, 128, 2, false>(x3, dz, x, tab, P, Psum, g, splits, per, s);
+          hipLaunchKernelGGL((conv_wgrad<128, 128, 2, true, false, true, true>), dim3(p.grid), dim3(kThreads), 0, s, dz, x, tab, P, Psum, g,
+                             p.m_tiles, p.k_tiles, p.splits, p.per);
+      } else if (fast) launch_wgrad<128, 128, 2, true>(x3, dz, x, tab, P, Psum, g, p, s);
+      else launch_wgrad<128, 128, 2, false>(x3, dz, x, tab, P, Psum, g, p, s);
       break;
     }
     case 64:
-      if (fast) launch_wgrad<64, 128, 2, true>(x3, dz, x, tab, P, Psum, g, splits, per, s);
-      else launch_wgrad<64, 128, 2, false>(x3, dz, x, tab, P, Psum, g, splits, per, s);
+      if (fast) launch_wgrad<64, 128, 2, true>(x3, dz, x, tab, P, Psum, g, p, s);
+      else launch_wgrad<64, 128, 2, false>(x3, dz, x, tab, P, Psum, g, p, s);
       break;
-    default: launch_wgrad<32, 128, 1, false>(x3, dz, x, tab, P, Psum, g, splits, per, s); break;
+    default: launch_wgrad<32, 128, 1, false>(x3, dz, x, tab, P, Psum, g, p, s); break;
   }
   DASAC_CHECK_LAUNCH("conv_wgrad");
   return DASAC_OK;
@@ -882,10 +813,10 @@ extern "C" int dasac_conv_wgrad_finish(const void* workspace, int Nb, int OH, in
                                        int tap0, dasac_stream_t stream) {
   DASAC_REQUIRE(workspace && w && dw, "conv_wgrad_finish: null pointer");
   DASAC_REQUIRE(!dot || (tap0 == 0 && Cin * taps == K), "conv_wgrad_finish: the dot term is defined for single-branch convolutions");
-  const WgradLayout l = wgrad_layout(M, K, Cin, Nb * OH * OW);
-  const int Mpad = l.Mpad, Kpad = l.Kpad, splits = l.splits;
+  const WgradPlan p = wgrad_plan(M, K, Cin, Nb * OH * OW);
+  const int Mpad = p.Mpad, Kpad = p.Kpad, splits = p.splits;
   const float* P = reinterpret_cast<const float*>(workspace);
-  const float* Psum = P + (size_t)splits * Mpad * Kpad;
+  const float* Psum = P + p.psum_offset;
   if (Cin < 32)      // lanes along the whole k axis (see the kernel); tap0 * Cin is this branch's first k
     hipLaunchKernelGGL(wgrad_reduce_scalar, dim3((Cin * taps + 63) / 64, M), dim3(256), 0, as_stream(stream), P + (size_t)tap0 * Cin, Psum,
                        splits, Mpad, Kpad, w, scale, dw, dot, sum_dz, Cin * taps, 1, 0, Cin);
@@ -904,39 +835,23 @@ extern "C" int dasac_conv_wgrad_finish(const void* workspace, int Nb, int OH, in
 
 // `batch` weight gradients over plain matrices as ONE launch (conv_wgrad_batched above; include/dasac_hip.h).  The pixel splits
 // are chosen over all batch * m_tiles * k_tiles tiles; 0 = the launch does not take this shape.
-extern "C" int dasac_conv_wgrad_batched_splits(int batch, int M, int C, int T) {
-  if (batch < 1 || batch > 65535 || M <= 0 || C <= 0 || T <= 0 || M % 128 || C % 128 || T % 4) return 0;
-  if ((int64_t)M * T * 4 >= (1ll << 31) || (int64_t)C * T * 4 >= (1ll << 31)) return 0;   // an entry's window, the scalar row offsets
-  if ((int64_t)batch * M * C * 4 > kMaxTensorBytes) return 0;                               // one split's slabs: at most 2^16 tiles
-  const int tiles = batch * (M / 128) * (C / 128);
-  constexpr int kMinPix = 256;                                 // at least 8 K-steps per split, at most 64 splits: as wgrad_splits
-  int max_splits = (T + kMinPix - 1) / kMinPix;
-  if (max_splits > 64) max_splits = 64;
-  const int splits = fill_rounds(tiles, max_splits, kNumCu * 3);
-  return (int64_t)splits * batch * M * C * 4 <= kMaxTensorBytes ? splits : 0;
-}
-
-extern "C" size_t dasac_conv_wgrad_batched_workspace(int batch, int M, int C, int T) {
-  const int splits = dasac_conv_wgrad_batched_splits(batch, M, C, T);
-  return (size_t)splits * ((size_t)batch * M * C + M) * sizeof(float);          // slabs + per-split row sums
-}
+extern "C" int dasac_conv_wgrad_batched_splits(int batch, int M, int C, int T) { return wgrad_batched_plan(batch, M, C, T).splits; }
+extern "C" size_t dasac_conv_wgrad_batched_workspace(int batch, int M, int C, int T) { return wgrad_batched_plan(batch, M, C, T).workspace_bytes; }
 
 extern "C" int dasac_conv_wgrad_batched(const float* a, const float* b, int batch, int M, int C, int T, int64_t a_stride,
                                         int64_t b_stride, int sum_entry, void* workspace, size_t ws_bytes, dasac_stream_t stream) {
   DASAC_REQUIRE(a && b && workspace, "conv_wgrad_batched: null pointer");
   DASAC_REQUIRE(sum_entry >= 0 && sum_entry < batch, "conv_wgrad_batched: sum_entry %d outside 0..batch-1", sum_entry);
-  const int splits = dasac_conv_wgrad_batched_splits(batch, M, C, T);
-  DASAC_REQUIRE(splits > 0, "conv_wgrad_batched: needs batch in 1..65535, M and C multiples of 128, T a multiple of 4, entries below 2 GiB "
+  const WgradBatchedPlan p = wgrad_batched_plan(batch, M, C, T);
+  DASAC_REQUIRE(p.splits > 0, "conv_wgrad_batched: needs batch in 1..65535, M and C multiples of 128, T a multiple of 4, entries below 2 GiB "
                             "and slabs inside the 4 GiB window (batch %d, M %d, C %d, T %d)", batch, M, C, T);
   DASAC_REQUIRE(a_stride >= (int64_t)M * T && b_stride >= (int64_t)C * T && a_stride % 4 == 0 && b_stride % 4 == 0,
                 "conv_wgrad_batched: a per-batch stride is smaller than one entry or not a multiple of 4 elements");
-  if (ws_bytes < dasac_conv_wgrad_batched_workspace(batch, M, C, T)) return fail(DASAC_EWORKSPACE, "conv_wgrad_batched: workspace too small");
-  int per = (T + splits - 1) / splits;
-  per = (per + kWgPix - 1) / kWgPix * kWgPix;
+  if (ws_bytes < p.workspace_bytes) return fail(DASAC_EWORKSPACE, "conv_wgrad_batched: workspace too small");
   float* P = reinterpret_cast<float*>(workspace);
-  float* Psum = P + (size_t)splits * batch * M * C;
-  const WgradBatch w{M, C, T, M / 128, C / 128, splits, per, sum_entry, a_stride, b_stride};
-  hipLaunchKernelGGL(conv_wgrad_batched, dim3(round_up_xcd(w.m_tiles * w.k_tiles * splits), batch), dim3(kThreads), 0, as_stream(stream), a, b, P, Psum, w);
+  float* Psum = P + p.psum_offset;
+  const WgradBatch w{M, C, T, p.m_tiles, p.k_tiles, p.splits, p.per, sum_entry, a_stride, b_stride};
+  hipLaunchKernelGGL(conv_wgrad_batched, dim3(p.grid, batch), dim3(kThreads), 0, as_stream(stream), a, b, P, Psum, w);
   DASAC_CHECK_LAUNCH("conv_wgrad_batched");
   return DASAC_OK;
 }
@@ -944,9 +859,9 @@ extern "C" int dasac_conv_wgrad_batched(const float* a, const float* b, int batc
 extern "C" int dasac_conv_wgrad_finish_expanded(const void* workspace, int Nb, int OH, int OW, int E, int Cin, float* dw,
                                                 int Cout, int taps, int tap0, int Cp, dasac_stream_t stream) {
   DASAC_REQUIRE(workspace && dw, "conv_wgrad_finish_expanded: null pointer");
-  const WgradLayout l = wgrad_layout(E, Cin, Cin, Nb * OH * OW);
+  const WgradPlan p = wgrad_plan(E, Cin, Cin, Nb * OH * OW);
   hipLaunchKernelGGL(wgrad_reduce_expanded, dim3(stream_grid((int64_t)Cout * taps * Cin, 256)), dim3(256), 0, as_stream(stream),
-                     reinterpret_cast<const float*>(workspace), l.splits, l.Mpad, l.Kpad, dw, Cout, Cin, taps, tap0, Cp);
+                     reinterpret_cast<const float*>(workspace), p.splits, p.Mpad, p.Kpad, dw, Cout, Cin, taps, tap0, Cp);
   DASAC_CHECK_LAUNCH("wgrad_reduce_expanded");
   return DASAC_OK;
 }

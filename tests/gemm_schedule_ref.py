@@ -1,5 +1,5 @@
 """The integer rules by which the conv GEMM (csrc/conv_gemm.hip) and the pixel-split weight gradient (csrc/conv_wgrad.hip) cut
-their work, restated in plain Python from the source, and a simulator that walks every block of a launch through them.
+their work (csrc/conv_plan.hpp holds them), restated in plain Python from the source, and a simulator that walks every block of a launch through them.
 
 Two halves that the kernels must keep in agreement:
   host rules   -- which schedule a shape gets, the split-K tail plan, the weight gradient's split count and workspace;
@@ -11,17 +11,17 @@ test_gpu_gemm_schedule_rules.py ties the host half to the shipped library, test_
 the plans this model says its cases reach."""
 from functools import lru_cache
 
-NUM_CU = 256                    # common.hpp: kNumCu
-NUM_XCD = 8                     # common.hpp: kNumXcd
-BK = 16                         # conv_common.hpp: kBK, the K-step of the forward / data-gradient GEMM
+NUM_CU = 256                    # chip.hpp: kNumCu
+NUM_XCD = 8                     # chip.hpp: kNumXcd
+BK = 16                         # conv_plan.hpp: kBK, the K-step of the forward / data-gradient GEMM
 TILE = 128                      # rows and pixels of the tile every hand-off schedule runs on
-SK_WORKERS_PER_CU = 3           # conv_gemm.hip: kSkWorkersPerCu
+SK_WORKERS_PER_CU = 3           # conv_plan.hpp: kSkWorkersPerCu
 SK_SLOTS = NUM_CU * SK_WORKERS_PER_CU      # 768: deposit / flag slots of a stream-K launch (kSkWorkers)
 TILE_SLOTS = NUM_CU * 4         # 1024: resident blocks of the tile-per-block kernel (kTileSlots)
 TAIL_SLOTS = 2048               # deposit / flag slots of the split-K tail (kTailSlots)
 SLOT_BYTES = TILE * TILE * 4    # one deposit: ACC_REGS * kThreads * 4 = 65536
-WG_PIX = 32                     # conv_wgrad.hip: kWgPix, pixels per K-step of the weight gradient
-MIN_PIX = 256                   # conv_wgrad.hip: kMinPix, fewest pixels per split
+WG_PIX = 32                     # conv_plan.hpp: kWgPix, pixels per K-step of the weight gradient
+MIN_PIX = 256                   # conv_plan.hpp: kWgMinPix, fewest pixels per split
 WG_SLOTS = NUM_CU * 3           # resident weight-gradient blocks
 MAX_SPLIT = 8                   # tail_plan: at most 8 K-ranges per tail tile
 MIN_STEPS = 8                   # tail_plan: at least 8 K-steps per piece
